@@ -14,7 +14,15 @@ Default (--mode throughput), the BASELINE.json metric:
   fresh child processes (torch.distributed.run, before this process makes any GPU call) and exits with
   their status; under torchrun, WORLD_SIZE must equal --gpus (exit 2 otherwise).
 
-  Beside `value` (never replacing it), each untimed or separately timed:
+  A plain run (`--gpus N --steps K --warmup W`) does only that: it builds the batch, warms up, times the K
+  steps, writes the last step's results when `--dump-outputs DIR` is given, and prints the line.
+
+  --dump-outputs DIR: what the K-th timed step left in the handles, as a caller fetches it (fetch_image,
+  fetch_stereo, overflow), for a fixed seeded sample of the batch's pairs, one float32 / float64 array per
+  DIR/<name>.npy (dump_outputs).  The batch is seeded, so two builds run with the same arguments can be
+  compared array for array.
+
+  --full adds, beside `value` (never replacing it), each untimed or separately timed:
   * parity of the bench's own workload: every handle's overflow word, 64 pairs per rank (first, last and
     evenly spaced pairs of every handle) bit for bit against the oracle extractor and the stereo
     restatement (the oracle on a thread pool);
@@ -31,7 +39,7 @@ Default (--mode throughput), the BASELINE.json metric:
     sequence, bit-exact against its golden, p50 latency per frame;
   * cpu_baseline (N = 1, before any GPU call): the reference's CPU path as restated by the oracle.
 
---mode frame: C3 alone as its own JSON line.
+--mode frame: C3 alone as its own JSON line.  --roofline-only: the standalone per-stage pass alone.
 
 Prints ONE JSON line on rank 0 (fields: DESIGN.md §5).
 """
@@ -206,6 +214,32 @@ def cpu_baseline(sample_pairs: int, width: int, height: int, nfeatures: int, pro
                      f"oracle C++ extractor (orb_oracle.cpp, -O3 -march=x86-64-v3 -ffp-contract=off) + "
                      f"oracle/stereo_loop.py (per-candidate Python popcount and per-shift SAD like Frame.py:161-279), "
                      f"{t1:.1f} s{allp}")
+    return out
+
+
+def make_batch(n_pairs: int, seed0: int, width: int, height: int, procs: int) -> np.ndarray:
+    """synth.make_batch's bytes (pair p from seed seed0 + p), the pairs rendered by `procs` forked processes
+    straight into one shared buffer: 512 KITTI pairs take tens of seconds on one core.  Forks, so it runs
+    BEFORE anything initialises the GPU."""
+    import mmap
+    import multiprocessing as mp
+    from pyorbslam_amd import synth
+    procs = min(procs, n_pairs // 4)  # a process is worth starting for a few pairs
+    if procs <= 1:
+        return synth.make_batch(n_pairs, seed0=seed0, width=width, height=height)
+    out = np.frombuffer(mmap.mmap(-1, 2 * n_pairs * height * width), np.uint8).reshape(2 * n_pairs, height, width)
+
+    def render(i):
+        for p in range(i, n_pairs, procs):
+            out[2 * p], out[2 * p + 1] = synth.make_pair(seed0 + p, width, height)
+
+    ps = [mp.get_context("fork").Process(target=render, args=(i,)) for i in range(procs)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join()
+    if any(p.exitcode != 0 for p in ps):
+        raise RuntimeError(f"batch rendering failed (exit codes {[p.exitcode for p in ps]})")
     return out
 
 
@@ -439,6 +473,52 @@ def max_over_ranks(v, dev, world):
     t = t.to(dev) if dist.get_backend() == "nccl" else t
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_MAX_BYTES = 48 << 20  # all files of one --dump-outputs directory together
+DUMP_MAX_PAIRS = 32
+
+
+def dump_outputs(out_dir, sh: Shard, seed: int = 0) -> dict:
+    """The results of the last enqueue of every handle of `sh`, as a caller fetches them, for a fixed sample
+    of the shard's pairs (PCG64(seed) choice without replacement, sorted; every pair when the shard has at
+    most DUMP_MAX_PAIRS and they fit in DUMP_MAX_BYTES), one array per <out_dir>/<name>.npy.  Rows beyond a
+    pair's keypoint count are zero.
+      sample_pairs (S,) f64: pair indices inside the shard;  overflow (handles,) f64: overflow words;
+      n_keypoints (S, 2) f64: left / right keypoint counts;
+      keypoints (S, 2, kp_cap, 6) f32: x, y, size, angle, response, octave;
+      descriptors (S, 2, kp_cap, 32) f32: the descriptor bytes;
+      u_right, depth, status, match_r (S, kp_cap) f32: fetch_stereo of the pair."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cap = max(f.kp_cap for f in sh.fes)
+    per_pair = cap * (2 * 6 + 2 * 32 + 4) * 4 + 3 * 8
+    S = max(1, min(sh.n_pairs, DUMP_MAX_PAIRS, DUMP_MAX_BYTES // per_pair))
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sample = np.sort(rng.choice(sh.n_pairs, size=S, replace=False))
+    offs = np.concatenate([[0], np.cumsum(sh.counts)])
+    arrays = {"sample_pairs": sample.astype(np.float64),
+              "overflow": np.array([f.overflow() for f in sh.fes], np.float64),
+              "n_keypoints": np.zeros((S, 2), np.float64),
+              "keypoints": np.zeros((S, 2, cap, 6), np.float32),
+              "descriptors": np.zeros((S, 2, cap, 32), np.float32)}
+    for name in ("u_right", "depth", "status", "match_r"):
+        arrays[name] = np.zeros((S, cap), np.float32)
+    for i, g in enumerate(sample.tolist()):
+        hi = int(np.searchsorted(offs, g, side="right")) - 1
+        f, p = sh.fes[hi], g - int(offs[hi])
+        for side in (0, 1):
+            k, d = f.fetch_image(2 * p + side)
+            arrays["n_keypoints"][i, side] = len(k)
+            for j, field in enumerate(("x", "y", "size", "angle", "response", "octave")):
+                arrays["keypoints"][i, side, :len(k), j] = k[field]
+            arrays["descriptors"][i, side, :len(k)] = d
+        st = f.fetch_stereo(p)
+        for name in ("u_right", "depth", "status", "match_r"):
+            arrays[name][i, :len(st[name])] = st[name]
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "pairs": S, "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def host_fed(sh: Shard, host, dev, world, steps, warmup, zero_copy: bool = False, h2d_streams: int = 1,
@@ -709,6 +789,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can report: cpu_baseline, parity "
+                         "against the oracle, gather (N > 1), C4 and its rank share, C5 (EuRoC), host-fed, the "
+                         "standalone per-stage pass and its rooflines, C3 (the options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (a fixed sample of the pairs) as DIR/<name>.npy")
     ap.add_argument("--pairs", type=int, default=512, help="stereo pairs per step per GPU (weak scaling)")
     ap.add_argument("--total-pairs", type=int, default=0,
                     help="strong scaling: this many pairs per step in total, sharded over the GPUs (C4: 64)")
@@ -766,13 +852,24 @@ def main():
         torch.cuda.set_device(dev)
         print(json.dumps(rank_share_measure(args, dev)), flush=True)
         return
-    extras = not args.roofline_only
+    step_timed = not args.roofline_only
+    extras = args.full and step_timed  # everything beside the timed steps and their dump
     cpu = None
     if world == 1 and args.cpu_sample > 0 and extras:
         cpus = job_cpus()
         procs = args.cpu_procs or cpus["cores"]
         cpu = cpu_baseline(args.cpu_sample, args.width, args.height, args.nfeatures, procs)
         cpu.update({k: v for k, v in cpus.items() if k != "cores"})
+
+    strong = args.total_pairs > 0
+    if strong:
+        first, P = shard(args.total_pairs, world, rank)
+        total = args.total_pairs
+    else:
+        first, P = rank * args.pairs, args.pairs
+        total = world * args.pairs
+    # the ranks of one host share its cores; rendered before the first GPU call (make_batch forks)
+    host = make_batch(P, first, args.width, args.height, job_cpus()["cores"] // world)
 
     import torch
     import torch.distributed as dist
@@ -790,22 +887,17 @@ def main():
     from pyorbslam_amd import _lib, synth
     from pyorbslam_amd import dist as D
 
-    strong = args.total_pairs > 0
-    if strong:
-        first, P = shard(args.total_pairs, world, rank)
-        total = args.total_pairs
-    else:
-        first, P = rank * args.pairs, args.pairs
-        total = world * args.pairs
-    host = synth.make_batch(P, seed0=first, width=args.width, height=args.height)
     images = torch.from_numpy(host).to(dev)
     elapsed = None
     sh = None
     n_handles = 0
-    if extras:
+    dumped = None
+    if step_timed:
         sh = Shard(images, P, args.streams, dev, args.width, args.height, args.nfeatures, args.lanes)
         n_handles = len(sh.fes)
         elapsed = timed(sh.step, args.steps, args.warmup, dev, world)
+        if args.dump_outputs:  # the last timed step's results, before anything else touches the handles
+            dumped = dump_outputs(Path(args.dump_outputs) / f"rank{rank}" if world > 1 else args.dump_outputs, sh)
 
     gather = None
     if extras and world > 1 and not args.no_gather:
@@ -813,7 +905,7 @@ def main():
 
     # ---- parity of the bench's own workload (untimed)
     parity = None
-    if sh is not None and not args.no_parity:
+    if extras and not args.no_parity:
         checked, ovf, bad = parity_check(sh.fes, sh.counts, host, args.width, args.height, args.nfeatures,
                                          args.parity_pairs)
         if world > 1:
@@ -868,7 +960,7 @@ def main():
 
     # ---- standalone per-stage pass: the same P pairs as one handle on one stream, HIP events per stage
     stage_ms = {}
-    if args.roofline_steps > 0 and rank == 0:
+    if args.roofline_steps > 0 and rank == 0 and (extras or args.roofline_only):
         del sh
         stage_ms = standalone_stages(images, P, args.width, args.height, args.nfeatures, args.roofline_steps, dev)
 
@@ -905,6 +997,8 @@ def main():
         })
         if dev_env and elapsed is not None:
             out["dev_env_ms_per_step"] = round(elapsed / args.steps * 1e3, 4)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if parity is not None:
             out.update(parity)
         if stage_ms:

@@ -76,6 +76,81 @@ def test_strong_scaling_shards(total):
         assert [s for s, _ in spans] == [sum(c for _, c in spans[:r]) for r in range(world)]
 
 
+def test_make_batch_renders_synth_bytes():
+    """bench.make_batch (forked renderers, shared buffer) against synth.make_batch, in a process of its own
+    as in the bench: it forks.  9 pairs on 2 processes (5 + 4), and 7 pairs (too few to fork for 2)."""
+    code = ("import bench; from pyorbslam_amd import synth\n"
+            "for n in (9, 7):\n"
+            "    got = bench.make_batch(n, 5, 160, 120, 2)\n"
+            "    assert got.shape == (2 * n, 120, 160) and got.dtype.name == 'uint8'\n"
+            "    assert got.tobytes() == synth.make_batch(n, seed0=5, width=160, height=120).tobytes()\n"
+            "print('same')\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "same", r.stdout[-1000:] + r.stderr[-3000:]
+
+
+def test_full_and_dump_outputs_are_options():
+    r = run_bench(["--gpus", "4", "--full", "--dump-outputs", "unused", "--cpu-sample", "0"],
+                  {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
+    assert r.returncode == 2 and "WORLD_SIZE=2 but --gpus 4" in r.stdout  # parsed; stopped by the world check
+
+
+def test_dump_outputs_layout(tmp_path):
+    """dump_outputs over two stand-in handles (3 + 2 pairs, global pair g = image pair of handle g // 3): every
+    pair lands in its row, rows are zero beyond the pair's count, every file is float32 / float64."""
+    import numpy as np
+    from pyorbslam_amd._lib import KP_DTYPE
+    cap = 6
+
+    class Handle:
+        kp_cap = cap
+
+        def __init__(self, first):
+            self.first = first
+
+        def overflow(self):
+            return 0
+
+        def fetch_image(self, i):
+            g, side = self.first + i // 2, i % 2
+            n = 1 + (2 * g + side) % cap
+            k = np.zeros(n, KP_DTYPE)
+            k["x"], k["y"], k["octave"] = 100 * g + side + np.arange(n) / 8, g, np.arange(n) % 8
+            return k, np.full((n, 32), (10 * g + side) % 251, np.uint8)
+
+        def fetch_stereo(self, p):
+            g = self.first + p
+            n = 1 + (2 * g) % cap
+            return dict(u_right=np.full(n, g + 0.5, np.float32), depth=np.full(n, -1, np.float32),
+                        status=np.ones(n, np.int8), match_r=np.arange(n, dtype=np.int32) - 1)
+
+    sh = types.SimpleNamespace(fes=[Handle(0), Handle(3)], counts=[3, 2], n_pairs=5)
+    info = bench.dump_outputs(tmp_path / "o", sh)
+    got = {p.stem: np.load(p) for p in (tmp_path / "o").iterdir()}
+    assert info["pairs"] == 5 and info["bytes"] == sum(a.nbytes for a in got.values())
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["sample_pairs"].tolist() == [0, 1, 2, 3, 4] and got["overflow"].tolist() == [0, 0]
+    assert got["keypoints"].shape == (5, 2, cap, 6) and got["descriptors"].shape == (5, 2, cap, 32)
+    for g in range(5):
+        for side in (0, 1):
+            n = 1 + (2 * g + side) % cap
+            assert got["n_keypoints"][g, side] == n
+            assert got["keypoints"][g, side, :n, 0].tolist() == [100 * g + side + j / 8 for j in range(n)]
+            assert got["keypoints"][g, side, :n, 5].tolist() == [j % 8 for j in range(n)]
+            assert (got["descriptors"][g, side, :n] == 10 * g + side).all()
+            assert not got["keypoints"][g, side, n:].any() and not got["descriptors"][g, side, n:].any()
+        n = 1 + (2 * g) % cap
+        assert (got["u_right"][g, :n] == g + 0.5).all() and (got["depth"][g, :n] == -1).all()
+        assert got["match_r"][g, :n].tolist() == list(range(-1, n - 1)) and not got["status"][g, n:].any()
+    # a larger shard: a fixed sample, the same on every call
+    big = types.SimpleNamespace(fes=[Handle(0)], counts=[100], n_pairs=100)
+    a = bench.dump_outputs(tmp_path / "a", big)
+    bench.dump_outputs(tmp_path / "b", big)
+    sa, sb = np.load(tmp_path / "a" / "sample_pairs.npy"), np.load(tmp_path / "b" / "sample_pairs.npy")
+    assert a["pairs"] == bench.DUMP_MAX_PAIRS == len(set(sa.tolist())) and np.array_equal(sa, sb)
+    assert np.load(tmp_path / "a" / "n_keypoints.npy")[:, 0].tolist() == [1 + (2 * int(g)) % cap for g in sa]
+
+
 def test_stamped_lookup(tmp_path, monkeypatch):
     monkeypatch.setattr(bench, "ROOT", tmp_path)
     (tmp_path / "profiles").mkdir()

@@ -14,7 +14,7 @@ for r in 1 2; do
   for sp in ${SPLITS:--1 3}; do
     m=$(ORBFE_OCT_SPLIT=$sp timeout -k 10 120 python tools/microbench.py --pairs 256 --rounds 3 2:0 2>/dev/null | tail -1) || exit 1
     st=$(ORBFE_OCT_SPLIT=$sp timeout -k 10 120 python tools/dbg/env_sweep.py --var ORBFE_NONE --rounds 2 =0 2>/dev/null | tail -1) || exit 1
-    eu=$(ORBFE_OCT_SPLIT=$sp timeout -k 10 200 python bench.py --width 752 --height 480 --nfeatures 1000 --cpu-sample 0 --no-c3 \
+    eu=$(ORBFE_OCT_SPLIT=$sp timeout -k 10 200 python bench.py --width 752 --height 480 --nfeatures 1000 --full --cpu-sample 0 --no-c3 \
          --no-c4 --no-host-fed --no-parity 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['stage_ms_standalone_step']['octree'])") || exit 1
     echo "round $r split $sp: octree $m | step $st | euroc pairs/s, octree ms: $eu"
   done

@@ -17,12 +17,12 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
   stage pytest_gpu 900 python -m pytest tests -m gpu -q -rf || { [ "$MODE" = test ] && exit 1; }
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  stage bench 600 python bench.py --steps 10 --warmup 3 --cpu-sample 2
+  stage bench 600 python bench.py --full --steps 10 --warmup 3 --cpu-sample 2
 fi
 if [ "$MODE" = dist2 ]; then
   # rehearse the N>1 path on one GPU: 2 ranks over gloo on cuda:0 (never the N=8 case)
   ORBFE_DIST_BACKEND=gloo stage dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --pairs 16 --gather
+      --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --pairs 16 --full
 fi
 if [ "$MODE" = prof ]; then
   export TMPDIR=/tmp
