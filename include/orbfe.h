@@ -32,8 +32,8 @@ extern "C" {
 /* ABI revision of this header (orbfe_abi_version() returns the library's).  4: ORBFE_NSTAGES = 5 (stage 3
  * describe, 4 stereo; the round-1 blur stage and orbfe_set_blur_fork are gone), orbfe_set_graphs,
  * orbfe_set_octree_kernel / orbfe_get_octree_kernel, orbfe_debug_detect_stats. */
-#define ORBFE_ABI_VERSION 6 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
-                               * sides above 4 095 px are accepted (kKeyXYBits) */
+#define ORBFE_ABI_VERSION 7 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
+                               * sides above 4 095 px are accepted (kKeyXYBits).  7: orbfe_kfdb_*, orbfe_bow_score */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -417,6 +417,47 @@ int orbfe_vocab_transform_device(orbfe_vocab_handle v, const uint8_t* d_desc32, 
                                  int32_t* d_word_id, int32_t* d_node_id, double* d_weight, void* hip_stream);
 /* Kernel time of the last orbfe_vocab_transform (ms, HIP events), for measurement. */
 int orbfe_vocab_last_ms(orbfe_vocab_handle v, float* ms);
+
+/* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
+ *
+ * A database of bag-of-words vectors that stays resident on the device, and the L1 score.  A vector is
+ * n distinct non-negative word ids in ascending order with one f64 weight each.  The host holds the
+ * master copy: create / add / erase / clear / stats make no device call; a query first uploads what
+ * the device has not seen yet.  When the slot table or the arena outgrows its capacity the capacity
+ * doubles and erased vectors are dropped from the arena (regrows counts these events); slot numbers
+ * of other vectors never change.
+ *
+ * Canonical L1 score: the terms (fabs(vi - wi) - fabs(vi)) - fabs(wi), vi the query's weight and wi the
+ * stored vector's, summed in ascending word id, sequentially, in IEEE double; the score is -sum / 2.0
+ * (-0.0 when no word is shared, as GeneralScoring.l1_score).  The reference sums in CPython's set
+ * order; for L1-normalised vectors the two differ by at most (n_common + 3) * 2^-52. */
+typedef struct orbfe_kfdb* orbfe_kfdb_handle;
+/* capacity hints (>= 1): vectors and arena entries (words over all vectors) */
+int orbfe_kfdb_create(int64_t kf_capacity, int64_t word_capacity, orbfe_kfdb_handle* out);
+int orbfe_kfdb_destroy(orbfe_kfdb_handle h);
+/* Appends one vector (n >= 0) and returns its slot; ORBFE_EINVAL unless the ids are distinct,
+ * non-negative and ascending. */
+int orbfe_kfdb_add(orbfe_kfdb_handle h, const int32_t* word, const double* weight, int32_t n, int64_t* slot);
+/* ORBFE_EINVAL for a slot that does not exist, ORBFE_ESTATE for one already erased. */
+int orbfe_kfdb_erase(orbfe_kfdb_handle h, int64_t slot);
+/* Empties the database (capacities stay); slot numbers restart at 0. */
+int orbfe_kfdb_clear(orbfe_kfdb_handle h);
+/* Any pointer may be NULL.  n_slots counts erased slots too; live_words sums the live vectors' lengths. */
+int orbfe_kfdb_stats(orbfe_kfdb_handle h, int64_t* n_slots, int64_t* n_live, int64_t* live_words,
+                     int64_t* kf_capacity, int64_t* word_capacity, int64_t* regrows);
+/* One launch over the whole database.  Per slot s < n_slots: common[s] = words shared with the query
+ * (0 for an erased slot), first[s] = smallest shared word id (-1 when none), score[s] = canonical L1
+ * score.  cap = length of the result arrays (ORBFE_ECAPACITY when below n_slots).  Host buffers,
+ * synchronous. */
+int orbfe_kfdb_query(orbfe_kfdb_handle h, const int32_t* q_word, const double* q_weight, int32_t nq,
+                     int32_t* common, int32_t* first, double* score, int64_t cap);
+/* The same kernel over n_vec vectors that are not in a database: vector v = word / weight[off[v] ..
+ * off[v + 1]), off[0] = 0. */
+int orbfe_bow_score(const int32_t* q_word, const double* q_weight, int32_t nq, const int64_t* off,
+                    const int32_t* word, const double* weight, int32_t n_vec,
+                    int32_t* common, int32_t* first, double* score);
+/* Kernel time of the last orbfe_kfdb_query (ms, HIP events; 0 for an empty database). */
+int orbfe_kfdb_last_ms(orbfe_kfdb_handle h, float* ms);
 
 #ifdef __cplusplus
 }

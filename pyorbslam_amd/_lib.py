@@ -17,7 +17,9 @@ LIB_PATH = Path(os.environ.get("ORBFE_LIB") or Path(__file__).resolve().parent /
 ORBFE_OK = 0
 ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ESTATE", -6: "EOVERFLOW", -7: "EFORMAT",
           -8: "EREJECT"}
+ORBFE_EINVAL = -1
 ORBFE_ECAPACITY = -4
+ORBFE_ESTATE = -5
 ORBFE_EFORMAT = -7
 ORBFE_EREJECT = -8
 
@@ -117,6 +119,17 @@ SIGNATURES = {
     "orbfe_vocab_transform_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p],
     "orbfe_vocab_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
+    "orbfe_kfdb_create": [C.c_int64, C.c_int64, C.POINTER(C.c_void_p)],
+    "orbfe_kfdb_destroy": [C.c_void_p],
+    "orbfe_kfdb_add": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],
+    "orbfe_kfdb_erase": [C.c_void_p, C.c_int64],
+    "orbfe_kfdb_clear": [C.c_void_p],
+    "orbfe_kfdb_stats": [C.c_void_p] + [C.POINTER(C.c_int64)] * 6,
+    "orbfe_kfdb_query": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_int64],
+    "orbfe_bow_score": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                        C.c_void_p, C.c_void_p],
+    "orbfe_kfdb_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

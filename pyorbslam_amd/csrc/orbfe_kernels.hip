@@ -3519,7 +3519,7 @@ __device__ __forceinline__ double py_round(double v) { return rint(v); }  // Pyt
 // LDS histogram -> block scan -> fill.  The order inside a bucket is irrelevant: k_stereo reduces
 // (distance, iR) lexicographically, which is the reference's first minimum in ascending iR.
 // Also writes the compact (x, octave) record of every right keypoint.  The right keypoints are read from the
-// octree's level keypoints (lvl_kp, lvl_count: x | y << 12 | score << 24 in level pixels), with the
+// octree's level keypoints (lvl_kp, lvl_count: (x + y * w) | score << 24, see kKeyXYBits / key_xy), with the
 // coordinates k_orb will write (ORBextractor.cpp:1094-1100: x = f32(level x) * scale[l] for l > 0) and the
 // index iR = the level-major position — so the buckets need the octree only, and the frame and batch paths
 // build them inside k_orb's launch (extra workgroups, stereo_bucket_pair) instead of after it.

@@ -1,0 +1,256 @@
+"""Drop-in for KeyFrameDatabase (KeyFrameDatabase.py): place recognition over a device-resident database.
+
+The reference keeps an inverted file (word id -> list of keyframes) and, per query, walks it in Python: one
+interpreter iteration per (query word x keyframe holding that word), then one l1_score call per keyframe that
+shares enough words.  Here every added keyframe's BoW vector is a slot of an orbfe_kfdb handle
+(pyorbslam_amd/csrc/orbfe_kfdb.hip) and a query is split in two:
+
+  device  ONE orbfe_kfdb_query launch, whatever the map size: per slot the number of shared words (common),
+          the smallest shared word id (first) and the canonical L1 score
+  host    replay_loop / replay_reloc: pure functions of those three arrays that reproduce the reference's
+          control flow and side effects (mnLoopQuery / mnLoopWords / mLoopScore, mnRelocQuery / mnRelocWords /
+          mRelocScore) and return the same candidate lists
+
+Why the replay is equivalent.  The reference meets keyframes in first-appearance order of its walk: query words
+ascending (a BoW vector is an OrderedDict sorted by word id), and within one word's list in insertion order.
+That is slot order sorted by (first[s], s) over the slots with common[s] > 0.  Per keyframe the walk's
+"+= 1 per shared word" adds up to common[s]; a keyframe added twice owns two slots and collects both.
+
+Differences from the reference, all listed in INTEGRATION.md section 6:
+  * scores use the canonical summation order (ascending word id) and differ from l1_score's CPython-set order by
+    at most (n_common + 3) * 2^-52;
+  * add() snapshots pKF.mBowVec; the reference reads pKFi.mBowVec again when it scores and when it erases;
+  * clear() empties the database; the reference's raises AttributeError (self.vocabulary_size does not exist).
+mvInvertedFile is not emulated: nothing outside the class reads it.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+
+import numpy as np
+
+from . import _lib
+from ._lib import call, lib, ptr
+
+
+def bow_arrays(bv):
+    """A BoW vector (dict word id -> weight) as ascending int32 word ids and their f64 weights."""
+    n = len(bv)
+    word = np.fromiter(bv.keys(), np.int64, n).astype(np.int32)
+    weight = np.fromiter(bv.values(), np.float64, n)
+    if n > 1 and not bool(np.all(word[1:] > word[:-1])):  # transform() returns sorted vectors; others are sorted here
+        o = np.argsort(word, kind="stable")
+        word, weight = word[o], weight[o]
+    return np.ascontiguousarray(word), np.ascontiguousarray(weight)
+
+
+def _visit_order(common, first):
+    """Slots in the order the reference's inverted-file walk first meets them."""
+    hit = np.flatnonzero(common > 0)
+    return hit[np.lexsort((hit, first[hit]))].tolist()
+
+
+def _retain(acc, best_acc):
+    keep = 0.75 * best_acc
+    out, seen = [], set()
+    for a, kf in acc:
+        if a > keep and kf not in seen:
+            out.append(kf)
+            seen.add(kf)
+    return out
+
+
+def replay_loop(slot_kf, common, first, score, query_id, connected, min_score):
+    """KeyFrameDatabase.detect_loop_candidates (KeyFrameDatabase.py:30-94) from the query's result arrays.
+    slot_kf[s] is the keyframe object of slot s (None once erased)."""
+    common = np.asarray(common)
+    sharing = []
+    for s in _visit_order(common, np.asarray(first)):
+        kf = slot_kf[s]
+        c = int(common[s])
+        if kf.mnLoopQuery != query_id:
+            kf.mnLoopWords = 0
+            if kf not in connected:
+                kf.mnLoopQuery = query_id
+                sharing.append((kf, s))
+                kf.mnLoopWords += c
+            else:  # never marked: every shared word resets it to 0 and adds 1
+                kf.mnLoopWords = 1
+        else:
+            kf.mnLoopWords += c
+    if not sharing:
+        return []
+    gate = int(max(kf.mnLoopWords for kf, _ in sharing) * 0.8)
+    scored = []
+    for kf, s in sharing:
+        if kf.mnLoopWords > gate:
+            sc = float(score[s])
+            kf.mLoopScore = sc
+            if sc >= min_score:
+                scored.append((sc, kf))
+    if not scored:
+        return []
+    acc, best_acc = [], min_score
+    for sc, kf in scored:
+        a, b, bk = sc, sc, kf
+        for k2 in kf.get_best_covisibility_key_frames(10):
+            if k2.mnLoopQuery == query_id and k2.mnLoopWords > gate:
+                a += k2.mLoopScore
+                if k2.mLoopScore > b:
+                    bk, b = k2, k2.mLoopScore
+        acc.append((a, bk))
+        if a > best_acc:
+            best_acc = a
+    return _retain(acc, best_acc)
+
+
+def replay_reloc(slot_kf, common, first, score, query_id):
+    """KeyFrameDatabase.detect_relocalization_candidates (KeyFrameDatabase.py:96-159).  No connected-set test; a
+    neighbour's mRelocScore is read whenever its mnRelocQuery matches, even when it did not pass the word gate
+    (a stale value, as in the reference)."""
+    common = np.asarray(common)
+    sharing = []
+    for s in _visit_order(common, np.asarray(first)):
+        kf = slot_kf[s]
+        if kf.mnRelocQuery != query_id:
+            kf.mnRelocWords = 0
+            kf.mnRelocQuery = query_id
+            sharing.append((kf, s))
+        kf.mnRelocWords += int(common[s])
+    if not sharing:
+        return []
+    gate = int(max(kf.mnRelocWords for kf, _ in sharing) * 0.8)
+    scored = []
+    for kf, s in sharing:
+        if kf.mnRelocWords > gate:
+            sc = float(score[s])
+            kf.mRelocScore = sc
+            scored.append((sc, kf))
+    if not scored:
+        return []
+    acc, best_acc = [], 0
+    for sc, kf in scored:
+        a, b, bk = sc, sc, kf
+        for k2 in kf.get_best_covisibility_key_frames(10):
+            if k2.mnRelocQuery != query_id:
+                continue
+            a += k2.mRelocScore
+            if k2.mRelocScore > b:
+                bk, b = k2, k2.mRelocScore
+        acc.append((a, bk))
+        best_acc = max(best_acc, a)
+    return _retain(acc, best_acc)
+
+
+class BowDatabase:
+    """Thin owner of an orbfe_kfdb handle: slots of BoW vectors and the one-launch query."""
+
+    def __init__(self, kf_capacity=1024, word_capacity=1 << 18):
+        self._h = None
+        h = C.c_void_p()
+        call("orbfe_kfdb_create", int(kf_capacity), int(word_capacity), C.byref(h))
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and _lib._lib is not None:
+            _lib._lib.orbfe_kfdb_destroy(h)
+
+    def add_arrays(self, word, weight) -> int:
+        word = np.ascontiguousarray(word, np.int32)
+        weight = np.ascontiguousarray(weight, np.float64)
+        if len(word) != len(weight):
+            raise ValueError("word ids and weights differ in length")
+        slot = C.c_int64()
+        call("orbfe_kfdb_add", self._h, ptr(word), ptr(weight), len(word), C.byref(slot))
+        return int(slot.value)
+
+    def add(self, bv) -> int:
+        return self.add_arrays(*bow_arrays(bv))
+
+    def erase(self, slot: int) -> None:
+        call("orbfe_kfdb_erase", self._h, int(slot))
+
+    def clear(self) -> None:
+        call("orbfe_kfdb_clear", self._h)
+
+    def stats(self) -> dict:
+        v = [C.c_int64() for _ in range(6)]
+        call("orbfe_kfdb_stats", self._h, *(C.byref(x) for x in v))
+        return dict(zip(("n_slots", "n_live", "live_words", "kf_capacity", "word_capacity", "regrows"),
+                        (int(x.value) for x in v)))
+
+    def query_arrays(self, word, weight):
+        """(common, first, score) per slot, one kernel launch."""
+        word = np.ascontiguousarray(word, np.int32)
+        weight = np.ascontiguousarray(weight, np.float64)
+        # a concurrent add may grow the table between stats and the query: ask again on ECAPACITY
+        while True:
+            n = self.stats()["n_slots"]
+            common = np.zeros(n, np.int32)
+            first = np.full(n, -1, np.int32)
+            score = np.zeros(n, np.float64)
+            rc = lib().orbfe_kfdb_query(self._h, ptr(word), ptr(weight), len(word), ptr(common), ptr(first),
+                                        ptr(score), n)
+            if rc != _lib.ORBFE_ECAPACITY:
+                _lib.check("orbfe_kfdb_query", rc)
+                return common, first, score
+
+    def query(self, bv):
+        return self.query_arrays(*bow_arrays(bv))
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_float()
+        call("orbfe_kfdb_last_ms", self._h, C.byref(ms))
+        return float(ms.value)
+
+
+class KeyFrameDatabase:
+    def __init__(self, voc):
+        self.mpVoc = voc
+        self.mMutex = threading.Lock()
+        self._db = BowDatabase()
+        self._slot_kf = []   # slot -> keyframe object, None once erased
+        self._kf_slots = {}  # keyframe object -> its live slots, ascending
+
+    # KeyFrameDatabase.py:11-17.  Adding a keyframe twice makes two slots (the reference appends it twice to
+    # every word's list).
+    def add(self, pKF):
+        with self.mMutex:
+            s = self._db.add(pKF.mBowVec)
+            assert s == len(self._slot_kf)
+            self._slot_kf.append(pKF)
+            self._kf_slots.setdefault(pKF, []).append(s)
+
+    # KeyFrameDatabase.py:19-25.  list.remove drops the first occurrence: the earliest live slot goes.
+    def erase(self, pKF):
+        with self.mMutex:
+            slots = self._kf_slots.get(pKF)
+            if not slots:
+                return
+            s = slots.pop(0)
+            if not slots:
+                del self._kf_slots[pKF]
+            self._db.erase(s)
+            self._slot_kf[s] = None
+
+    def clear(self):
+        with self.mMutex:
+            self._db.clear()
+            self._slot_kf = []
+            self._kf_slots = {}
+
+    def detect_loop_candidates(self, pKF, min_score):
+        connected = pKF.get_connected_key_frames()
+        with self.mMutex:
+            common, first, score = self._db.query(pKF.mBowVec)
+            return replay_loop(self._slot_kf, common, first, score, pKF.mnId, connected, min_score)
+
+    def detect_relocalization_candidates(self, F):
+        with self.mMutex:
+            common, first, score = self._db.query(F.mBowVec)
+            return replay_reloc(self._slot_kf, common, first, score, F.mnId)
+
+    def last_kernel_ms(self) -> float:
+        return self._db.last_kernel_ms()

@@ -7,6 +7,11 @@ out child-run-contiguous in HBM, and every descriptor of a frame (or of many fra
 k_vocab_descend launch (pyorbslam_amd/csrc/orbfe_vocab.hip).  The host keeps only what is inherently
 sequential: threading the previous feature's node id through descents that stop above the node level,
 and accumulating the BoW weights in feature order so every float sum matches the reference's.
+
+score / score_many (TemplatedVocabulary.py:99-106): "L1_NORM", the scoring System.py:38 builds the vocabulary
+with, runs on the device (k_bow_score, pyorbslam_amd/csrc/orbfe_kfdb.hip) in the canonical summation order
+(ascending word id; within (n_common + 3) * 2^-52 of l1_score's CPython-set order).  The five other scoring
+strings are plain host restatements of ScoringObject.py, per pair.
 """
 from __future__ import annotations
 
@@ -19,6 +24,71 @@ from . import _lib
 from ._lib import ORBFE_EFORMAT, ORBFE_EREJECT, VocabInfo, call, check, lib, ptr
 
 
+# ScoringObject.py:30-92, restated for the host (no device path)
+def _l2_score(v1, v2):
+    shared = set(v1.keys()) & set(v2.keys())
+    dot = sum(v1[k] * v2[k] for k in shared)
+    if dot >= 1.0:
+        return 1.0
+    return 1.0 - np.sqrt(1.0 - dot)
+
+
+def _chi_square_score(v1, v2):
+    score = 0.0
+    for k in set(v1.keys()) & set(v2.keys()):
+        vi, wi = v1[k], v2[k]
+        if vi + wi != 0.0:
+            score += (vi * wi) / (vi + wi)
+    return score * 2.0
+
+
+def _kl_score(v1, v2):
+    log_eps = np.log(np.finfo(float).eps)
+    score = 0.0
+    for k in v1.keys():
+        vi, wi = v1[k], v2.get(k, 0)
+        if wi > 0 and vi > 0:
+            score += vi * np.log(vi / wi)
+        elif vi > 0:
+            score += vi * (np.log(vi) - log_eps)
+    return score
+
+
+def _bhattacharyya_score(v1, v2):
+    return sum(np.sqrt(v1[k] * v2[k]) for k in set(v1.keys()) & set(v2.keys()))
+
+
+def _dot_product_score(v1, v2):
+    return sum(v1[k] * v2[k] for k in set(v1.keys()) & set(v2.keys()))
+
+
+_HOST_SCORING = {"L2_NORM": _l2_score, "CHI_SQUARE": _chi_square_score, "KL": _kl_score,
+                 "BHATTACHARYYA": _bhattacharyya_score, "DOT_PRODUCT": _dot_product_score}
+
+
+def l1_score_many(bv, others):
+    """Canonical L1 score of bv against every vector of others: ONE orbfe_bow_score launch."""
+    from .kfdb import bow_arrays
+    others = list(others)
+    if not others:
+        return []
+    qw, qv = bow_arrays(bv)
+    parts = [bow_arrays(o) for o in others]
+    off = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(w) for w, _ in parts], out=off[1:])
+    word = np.ascontiguousarray(np.concatenate([w for w, _ in parts]), np.int32)
+    weight = np.ascontiguousarray(np.concatenate([v for _, v in parts]), np.float64)
+    n = len(parts)
+    common, first, score = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+    call("orbfe_bow_score", ptr(qw), ptr(qv), len(qw), ptr(off), ptr(word), ptr(weight), n, ptr(common), ptr(first),
+         ptr(score))
+    return score.tolist()
+
+
+def _l1_score(v1, v2):
+    return l1_score_many(v1, [v2])[0]
+
+
 class TemplatedVocabulary:
     def __init__(self, k=10, L=5, weighting="TF_IDF", scoring="L1_NORM"):
         self.k = k
@@ -26,6 +96,10 @@ class TemplatedVocabulary:
         self.weighting = weighting
         self.scoring = scoring
         self._h = None
+        # the scoring function is fixed here from the constructor string (create_scoring_object,
+        # TemplatedVocabulary.py:83-94); load_from_text_file later overwrites self.scoring with the header
+        # integer without changing it.  An unknown string leaves None: score() then raises TypeError.
+        self.scoring_object = _l1_score if scoring == "L1_NORM" else _HOST_SCORING.get(scoring)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -92,6 +166,16 @@ class TemplatedVocabulary:
     # TemplatedVocabulary.py:96-97
     def size(self) -> int:
         return 0 if self._h is None else int(self.info().n_words)
+
+    # TemplatedVocabulary.py:99-106
+    def score(self, bow_vector1, bow_vector2):
+        return self.scoring_object(bow_vector1, bow_vector2)
+
+    def score_many(self, bow_vector, bow_vectors):
+        """[score(bow_vector, b) for b in bow_vectors]; under L1_NORM one kernel launch for all of them."""
+        if self.scoring_object is _l1_score:
+            return l1_score_many(bow_vector, bow_vectors)
+        return [self.scoring_object(bow_vector, b) for b in bow_vectors]
 
     def descend(self, features, levels_up=4):
         """Raw per-descriptor (word id, node id at depth L - levels_up or -1, weight): one launch."""
