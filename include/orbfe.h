@@ -339,9 +339,23 @@ int orbfe_profile_begin(orbfe_handle h, int32_t max_batches);
 int orbfe_profile_read(orbfe_handle h, float* ms_per_stage, int32_t* n_batches);
 
 /* Kernel micro-benchmark on the inputs of the last batch (development aid, not part of the drop-in):
- * runs stage `stage` (0 resize, 1 detect, 2 octree, 3 describe, 4 stereo) in ablation variant `variant`
- * (0 = production kernel) `reps` times on the handle's last stream and returns the average ms.
- * Variants other than 0 overwrite stage outputs with garbage: re-run the batch afterwards. */
+ * runs stage `stage` in launch shape `variant` once to warm up and then `reps` times on the handle's last
+ * stream, and returns the average ms.  Variant 0 is the launcher's automatic choice; the others force one of
+ * the choices a launcher otherwise makes from the batch size.  Every accepted variant runs a production kernel
+ * and leaves the stage's correct outputs behind, so the handle's results stay valid.  Any other stage or
+ * variant number returns ORBFE_EINVAL.
+ *
+ *   stage       variant
+ *   0 resize    0 / 7  one launch per level (also for batches that run the cascade)
+ *               5      one launch per level, without the remainder wave
+ *               6      the one-launch cascade with the automatic strip count (small batches only)
+ *               100+S  the one-launch cascade with S strips, 1 <= S <= rows of the top level (or the next
+ *                      count that fits the LDS)
+ *   1 detect    0 automatic, 4 / 5: four cells / one cell per wave
+ *   2 octree    0 automatic, 1 / 2: 256 / 512 threads per workgroup; with the per-candidate kernel
+ *               selected (orbfe_set_octree_kernel): 0 only
+ *   3 describe  0 automatic, 1 / 9 / 2: eight / four / two keypoints per wave (12 = 2)
+ *   4 stereo    0 */
 int orbfe_microbench(orbfe_handle h, int32_t stage, int32_t variant, int32_t reps, float* ms);
 
 /* ---- diagnostics (stage outputs of the last orbfe_extract, image 0) ------------------------------

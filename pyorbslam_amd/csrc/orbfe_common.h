@@ -77,21 +77,15 @@ struct CellGeo {
 };
 
 // Resize column entry.
-#ifndef ORBFE_RS_ROWS
-#define ORBFE_RS_ROWS 16  // experiment switch (tools/dbg/build_variant.sh)
-#endif
-constexpr int kRsRows = ORBFE_RS_ROWS;  // k_resize output rows per workgroup (band)
-// batches of fewer images than this run the small-batch (latency) variants: the one-launch pyramid cascade,
+constexpr int kRsRows = 16;  // k_resize_rows output rows per workgroup (band)
+// batches of fewer images than this run the small-batch (latency) paths: the one-launch pyramid cascade,
 // one FAST cell per wave, 1 024-thread octree workgroups
 constexpr int kSmallBatchImages = 32;
 // k_octree candidates kept in LDS (with the node arrays <= 80 KiB: two workgroups per CU)
 constexpr int kOctKeys = 7424;
 // k_octree_bins: keys per block of the first sweep's key -> cell table (log2); a key walks forward from its
 // block's first cell over the cells the block spans
-#ifndef ORBFE_OB_KBLK_SH
-#define ORBFE_OB_KBLK_SH 4  // 16 keys (64: octree 0.421 -> 0.408 ms standalone, 8 pairs 32.9 -> 31.8 us; 8: LDS, 0.574)
-#endif
-constexpr int kObKblkSh = ORBFE_OB_KBLK_SH;
+constexpr int kObKblkSh = 4;  // 16 keys (64: octree 0.421 -> 0.408 ms standalone, 8 pairs 32.9 -> 31.8 us; 8: LDS, 0.574)
 constexpr int kObKblkMax = 32768 >> kObKblkSh;  // table entries (keys past them walk from the last one)
 
 struct ResizeX {

@@ -12,10 +12,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "orbfe_common.h"
@@ -859,7 +861,7 @@ void extract_range(orbfe_ctx& c, const uint8_t* d_in, int64_t pitch, int i0, int
                                     n, s, zero_ovf ? c.d_overflow.p : nullptr));
     } else {
         for (int l = 1; l < g.nlevels; ++l)
-            HIPCK(launch_resize(g, l, in, pitch, ws, c.d_xt.p, c.d_yt.p, n, s, 0,
+            HIPCK(launch_resize(g, l, in, pitch, ws, c.d_xt.p, c.d_yt.p, n, s, true,
                                 zero_ovf && l == 1 ? c.d_overflow.p : nullptr));
     }
     if (prof) prof_mark(c, s, 1);
@@ -1913,17 +1915,48 @@ int orbfe_microbench(orbfe_handle h, int32_t stage, int32_t variant, int32_t rep
         const Geo& g = h->geo;
         const int n = h->last_images;
         hipStream_t s = h->last_stream;
-        hipEvent_t e0, e1;
-        HIPCK(hipEventCreate(&e0));
-        HIPCK(hipEventCreate(&e1));
+        // The variant numbers (table in orbfe.h) as the launchers' arguments; every other number is refused.
+        // arg: stage 0 the cascade's strip count (0: per-level launches), 1 cells per wave, 2 threads,
+        // 3 keypoints per wave; 0 = the launcher's automatic choice
+        int arg = 0;
+        bool remainder_wave = true, cascade = false;
+        auto pick = [&](std::initializer_list<std::pair<int, int>> tab) {
+            for (const auto& e : tab)
+                if (e.first == variant) return e.second;
+            throw Error(ORBFE_EINVAL, "bad variant for this stage");
+        };
+        switch (stage) {
+            case 0:
+                // 0 / 7: the per-level launches whatever the batch size, 5: without the remainder wave; 6: the
+                // one-launch cascade with the automatic strip count for this batch, 100 + S: with S strips
+                cascade = variant == 6 || variant >= 100;
+                arg = variant >= 100 ? variant - 100 : pick({{0, 0}, {5, 0}, {6, cascade_strips(*h, n)}, {7, 0}});
+                // a strip holds at least one row of the top level (resize_strips)
+                if (cascade && (arg <= 0 || arg > g.lv[g.nlevels - 1].h))
+                    throw Error(ORBFE_EINVAL, "no cascade strip count for this batch");
+                remainder_wave = variant != 5;
+                break;
+            case 1: arg = pick({{0, 0}, {4, 4}, {5, 1}}); break;
+            case 2: arg = g.oct_v == 0 ? pick({{0, 0}, {1, 256}, {2, 512}}) : pick({{0, 0}}); break;
+            case 3: arg = pick({{0, 0}, {1, 8}, {9, 4}, {2, 2}, {12, 2}}); break;
+            case 4: arg = pick({{0, 0}}); break;
+            default: throw Error(ORBFE_EINVAL, "bad stage");
+        }
+        struct Events {  // destroyed on every way out, a throwing run() included
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            ~Events() {
+                if (e0) (void)hipEventDestroy(e0);
+                if (e1) (void)hipEventDestroy(e1);
+            }
+        } ev;
+        HIPCK(hipEventCreate(&ev.e0));
+        HIPCK(hipEventCreate(&ev.e1));
         auto run = [&] {
             switch (stage) {
                 case 0:
-                    // variant 6: the one-launch cascade with the automatic strip count for this batch, 100 + S:
-                    // with S strips (tools/microbench.py); 7: the per-level launches whatever the batch size
-                    if (variant == 6 || variant >= 100) {
+                    if (cascade) {
                         orbfe_ctx::Cascade* cs = nullptr;
-                        for (int S = variant >= 100 ? variant - 100 : cascade_strips(*h, n); S > 0; S += 4) {
+                        for (int S = arg; S > 0; S += 4) {
                             if (!(cs = find_cascade(*h, S))) {
                                 std::unique_ptr<orbfe_ctx::Cascade> ns = resize_strips(*h, S);
                                 if (ns) h->cascades.push_back(std::move(ns));
@@ -1938,47 +1971,35 @@ int orbfe_microbench(orbfe_handle h, int32_t stage, int32_t variant, int32_t rep
                     }
                     for (int l = 1; l < g.nlevels; ++l)
                         HIPCK(launch_resize(g, l, h->last_in, h->last_pitch, h->d_ws.p, h->d_xt.p, h->d_yt.p, n, s,
-                                            variant == 7 ? 0 : variant));
+                                            remainder_wave));
                     break;
                 case 1:
                     HIPCK(launch_detect(g, h->d_cells.p, h->last_in, h->last_pitch, h->d_ws.p, h->d_cell_count.p,
-                                        h->d_slots.p, n, s, variant));
+                                        h->d_slots.p, n, s, arg));
                     break;
                 case 2:
                     HIPCK(launch_octree(g, h->d_cells.p, h->d_cell_count.p, h->d_slots.p, h->d_octab.p, h->d_kd.p,
                                         h->d_kn.p, h->d_lvl_kp.p, h->d_lvl_count.p, h->d_overflow.p, h->maxcell, n, s,
-                                        variant));
+                                        arg));
                     break;
                 case 3:
-                    // variant 0: k_orb (production), 8: 8-wave workgroups, 12 / 9 / 10: 2 / 4 / 16 keypoints per
-                    // wave (the round-1 unfused k_blur + k_describe pair is in the git history, round 1)
                     HIPCK(launch_orb(g, h->last_in, h->last_pitch, h->d_ws.p, h->d_lvl_kp.p, h->d_lvl_count.p,
-                                     h->d_kps.p, h->d_desc.p, h->d_count.p, n, h->d_orb.p, s, variant == 12 ? 2 : variant));
+                                     h->d_kps.p, h->d_desc.p, h->d_count.p, n, h->d_orb.p, s, arg));
                     break;
-                case 4:
+                default:
                     if (h->last_pairs <= 0) throw Error(ORBFE_ESTATE, "no stereo batch");
                     enqueue_stereo_batch(*h, h->last_pairs, h->last_bf, h->last_fx, s);
                     break;
-                case 5:
-                    // the HBM writes a blurred pyramid would add (every level of every image, w x h bytes each):
-                    // the lower bound of its cost in any design that writes one
-                    h->d_shear.ensure((size_t)n * (size_t)g.shear_bytes);
-                    HIPCK(hipMemsetD8Async((hipDeviceptr_t)h->d_shear.p, 0x5A, (size_t)n * (size_t)g.shear_bytes, s));
-                    break;
-                default:
-                    throw Error(ORBFE_EINVAL, "bad stage");
             }
         };
         run();  // warm
-        HIPCK(hipEventRecord(e0, s));
+        HIPCK(hipEventRecord(ev.e0, s));
         for (int r = 0; r < reps; ++r) run();
-        HIPCK(hipEventRecord(e1, s));
-        HIPCK(hipEventSynchronize(e1));
+        HIPCK(hipEventRecord(ev.e1, s));
+        HIPCK(hipEventSynchronize(ev.e1));
         float t = 0.f;
-        HIPCK(hipEventElapsedTime(&t, e0, e1));
+        HIPCK(hipEventElapsedTime(&t, ev.e0, ev.e1));
         *ms = t / reps;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
     });
 }
 

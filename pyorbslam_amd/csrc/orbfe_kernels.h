@@ -82,11 +82,17 @@ struct UndistortArgs {
 };
 hipError_t launch_undistort(const float* xy_in, int n, int stride_in, float* xy_out, const UndistortArgs& a,
                             hipStream_t s);
+// The launchers' trailing choice arguments select between production paths that compute the same bits; their
+// defaults are the automatic choice from the batch size, and a value no kernel is built for is
+// hipErrorInvalidValue.
+// remainder_wave = false: every 64-group chunk of a row is row-uniform, no remainder wave
 // zero_word (optional): a device int the launch sets to 0 (the batch's overflow word, cleared without a memset)
 hipError_t launch_resize(const Geo& g, int l, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
-                         const ResizeY* yt, int n_images, hipStream_t s, int variant = 0, int* zero_word = nullptr);
+                         const ResizeY* yt, int n_images, hipStream_t s, bool remainder_wave = true,
+                         int* zero_word = nullptr);
+// cells_per_wave: 0 automatic, or 4 / 1 forced; stats (optional): the counters of orbfe_debug_detect_stats
 hipError_t launch_detect(const Geo& g, const CellGeo* cells, const uint8_t* in, int64_t in_pitch, const uint8_t* ws,
-                         int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int variant = 0,
+                         int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int cells_per_wave = 0,
                          int* stats = nullptr);
 size_t octree_lds_bytes(const Geo& g, int maxcell);
 size_t octree_bins_lds_bytes(const Geo& g, int maxcell);
@@ -101,17 +107,19 @@ hipError_t prepare_resize_cascade(int lds_bytes);
 // raise the octree kernels' dynamic-LDS attribute for this geometry (outside any stream capture)
 hipError_t prepare_octree(const Geo& g, int maxcell);
 // Geo::oct_v selects k_octree_bins (0) or the per-candidate pass kernel k_octree (1); octab: the
-// per-level Morton tables of k_octree_bins (orbfe_host.hip octree_tables)
+// per-level Morton tables of k_octree_bins (orbfe_host.hip octree_tables); threads: 0 automatic, or 256 / 512
+// forced (k_octree_bins only: k_octree has one shape)
 hipError_t launch_octree(const Geo& g, const CellGeo* cells, const int* cell_count, const uint32_t* slots,
                          const uint32_t* octab, uint32_t* kd, uint16_t* kn, uint32_t* lvl_kp, int* lvl_count, int* overflow,
-                         int maxcell, int n_images, hipStream_t s, int variant = 0, long long* prof = nullptr);
+                         int maxcell, int n_images, hipStream_t s, int threads = 0, long long* prof = nullptr);
 // fused IC angle + 7x7 blur of each keypoint's neighbourhood + steered BRIEF (replaces k_blur + k_describe)
 // bucket (optional): the stereo row buckets of pairs 0 .. n_bucket - 1 are built by extra workgroups of the
 // same launch (they need the octree's level keypoints only); only when orb_fuses_bucket(g)
+// keypoints_per_wave: 0 automatic, or 8 / 4 / 2 forced
 hipError_t launch_orb(const Geo& g, const uint8_t* in, int64_t in_pitch, const uint8_t* ws, const uint32_t* lvl_kp,
                       const int* lvl_count, orbfe_keypoint* out_kp, uint8_t* out_desc, int* out_count, int n_images,
-                      const uint32_t* tab, hipStream_t s, int variant = 0, const StereoArgs* bucket = nullptr,
-                      int n_bucket = 0);
+                      const uint32_t* tab, hipStream_t s, int keypoints_per_wave = 0,
+                      const StereoArgs* bucket = nullptr, int n_bucket = 0);
 bool orb_fuses_bucket(const Geo& g);
 // k_orb's item table (orb_tables on the host): 192 horizontal items + 256 centroid slots x 4 dwords
 constexpr int kOrbTabWords = 192 + 256 * 4;

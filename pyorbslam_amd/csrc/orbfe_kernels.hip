@@ -226,13 +226,14 @@ __device__ int block_sum(int v, int* red) {
 }
 
 // ------------------------------------------------------------------------------- k_resize
-// One 256-thread workgroup per band of kRsRows output rows of level l (l >= 1), full width.
+// The per-level kernel (k_resize_rows) and the one-launch cascade (k_resize_cascade) share this scheme for a
+// band of output rows of level l (l >= 1), full width:
 //  * staging: the source rows the band reads (sy0(first) .. sy1(last) of level l-1) are one contiguous
 //    byte range in memory for every level (stride W for the input, the 16-byte pitch for derived levels),
 //    so they are copied to LDS as a flat run of aligned dwords, every load issued before the first wait;
 //    LDS byte sh0 + r * stride + c holds source row ys_lo + r, column c (sh0 = the range's misalignment).
 //  * the level's x coefficients become, per 4-pixel group, v_perm selectors into an 8-byte tap window
-//    starting at the group's first sx plus the packed (a0, a1) weights, stored once per block as SoA.
+//    starting at the group's first sx plus the packed (a0, a1) weights.
 //  * compute: per group and row, 2 x (3 LDS dwords, 2 v_alignbyte, 4 v_perm + 4 v_dot2_u32_u16) for the
 //    horizontal taps, then OpenCV's vertical rounding; one aligned dword store per 4 output pixels.
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -249,131 +250,13 @@ __device__ __forceinline__ uint32_t resize_tap3(uint32_t A3, uint32_t aa) {
 }
 constexpr int kRsSlots = 16;  // staged dwords per thread per pass
 
-#ifdef ORBFE_DEV_VARIANTS  // the round-2 item-mapped kernel, for tools/microbench.py (tools/dbg/build_variant.sh)
-template <int V>  // V: 0 full kernel; ablations for tools/microbench.py: 1 staging only, 2 compute only
-__global__ __launch_bounds__(256) void k_resize(Geo g, int l, const uint8_t* __restrict__ in, int64_t in_pitch,
-                                                uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
-                                                const ResizeY* __restrict__ yt) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
-    const LevelGeo& L = g.lv[l];
-    uint4* s_xa = (uint4*)rs_lds;                        // per group: v_perm selectors, then (a0, a1) weights
-    int* s_sx0 = (int*)(s_xa + 2 * L.rs_ngrp);
-    // per output row of the band: LDS byte offsets of its two source rows' starts and b0 << 12, b1 << 12
-    uint4* s_ry = (uint4*)(s_sx0 + L.rs_ngrp);
-    uint32_t* s_src = (uint32_t*)(s_ry + kRsRows);       // staged source rows
-    const LevelGeo& P = g.lv[l - 1];
-    int bx, img;
-    xcd_block(bx, img);  // neighbouring bands share source rows: keep them in one L2
-    const int t = threadIdx.x;
-    const int dy0 = bx * kRsRows, nrow = min(kRsRows, L.h - dy0);
-    const int ngrp = (L.w + 3) >> 2;
-    int sstride;
-    const uint8_t* src = level_ptr(g, l - 1, in, in_pitch, ws, img, &sstride);
-    const int ys_lo = yt[L.ytab_off + dy0].sy0, ys_hi = yt[L.ytab_off + dy0 + nrow - 1].sy1;
-    const uintptr_t a0 = (uintptr_t)(src + (int64_t)ys_lo * sstride);
-    const int sh0 = (int)(a0 & 3);
-    const uint32_t* gsrc = (const uint32_t*)(a0 - sh0);
-    const int ndw = ((ys_hi - ys_lo) * sstride + P.w + sh0 + 3) >> 2;
-    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-    const uint32_t src_lds = (uint32_t)(uintptr_t)(lds_u32*)s_src;  // LDS address of the staged rows
-    for (int base = 0; base < (V == 2 ? 0 : ndw); base += 256 * kRsSlots) {
-        uint32_t v[kRsSlots];
-#pragma unroll
-        for (int k = 0; k < kRsSlots; ++k) {
-            const int i = base + t + 256 * k;
-            v[k] = i < ndw ? gsrc[i] : 0u;
-        }
-        if (base == 0) {
-            const uint4* xg = (const uint4*)(xt + L.xtab_off);  // xtab_off is a multiple of 4
-            for (int gi = t; gi < ngrp; gi += 256) {
-                const uint4 q0 = xg[2 * gi], q1 = xg[2 * gi + 1];
-                const uint32_t sx0 = q0.x;
-                // byte r and r + 1 of the window as a u16 pair (selector 0x0c = zero byte)
-                auto sel = [&](uint32_t sx) { const uint32_t r = sx - sx0; return r | ((r + 1) << 16) | 0x0c000c00u; };
-                s_xa[2 * gi] = uint4{sel(q0.x), sel(q0.z), sel(q1.x), sel(q1.z)};
-                s_xa[2 * gi + 1] = uint4{q0.y, q0.w, q1.y, q1.w};
-                s_sx0[gi] = (int)sx0;
-            }
-            if (t < nrow) {
-                const ResizeY y = yt[L.ytab_off + dy0 + t];
-                s_ry[t] = uint4{src_lds + (uint32_t)(sh0 + (y.sy0 - ys_lo) * sstride),
-                                src_lds + (uint32_t)(sh0 + (y.sy1 - ys_lo) * sstride), (uint32_t)y.b0 << 12,
-                                (uint32_t)y.b1 << 12};
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kRsSlots; ++k) {
-            const int i = base + t + 256 * k;
-            if (i < ndw) s_src[i] = v[k];
-        }
-    }
-    if (V == 2 && t < nrow) {
-        const ResizeY y = yt[L.ytab_off + dy0 + t];
-        s_ry[t] = uint4{src_lds + (uint32_t)(sh0 + (y.sy0 - ys_lo) * sstride),
-                        src_lds + (uint32_t)(sh0 + (y.sy1 - ys_lo) * sstride), (uint32_t)y.b0 << 12, (uint32_t)y.b1 << 12};
-    }
-    __syncthreads();
-    uint8_t* dst = ws + (int64_t)img * g.ws_bytes + L.ws_off + (int64_t)dy0 * L.pitch;
-    if (V == 1) {
-        if (t == 0) dst[0] = ((const uint8_t*)s_src)[sh0];
-        return;
-    }
-    const int step_r = 256 / ngrp, step_g = 256 - step_r * ngrp;
-    int rr = t / ngrp, grp = t - rr * ngrp;
-    while (rr < nrow) {
-        const uint4 ry = s_ry[rr];  // (LDS address of source row 0, of row 1, b0 << 12, b1 << 12)
-        const uint4 e = s_xa[2 * grp], aa = s_xa[2 * grp + 1];
-        const int sx0 = s_sx0[grp];
-        auto taps = [&](uint32_t roff, uint32_t (&h)[4]) {
-            const int A = (int)roff + sx0, o = A & 3;
-            lds_u32* w = (lds_u32*)(uintptr_t)(uint32_t)(A - o);
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-            const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o);
-            // S[sx] * a0 + S[sx + 1] * a1 (a1 = 0 past xmax: OpenCV's S[sx] * 2048)
-            h[0] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.x)),
-                                          __builtin_bit_cast(us2, aa.x), 0u, false);
-            h[1] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.y)),
-                                          __builtin_bit_cast(us2, aa.y), 0u, false);
-            h[2] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.z)),
-                                          __builtin_bit_cast(us2, aa.z), 0u, false);
-            h[3] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.w)),
-                                          __builtin_bit_cast(us2, aa.w), 0u, false);
-        };
-        uint32_t h0[4], h1[4];
-        taps(ry.x, h0);
-        taps(ry.y, h1);
-        // OpenCV VResizeLinearVec_32s8u: v_mul_hi(S >> 4, beta) on int16 lanes, (x + 2) >> 2; h >> 4 <= 32640 so
-        // the int16 pack never saturates and (x * b) >> 16 == mul_hi(x, b << 16) == mul_hi(x << 4, b << 12) ==
-        // mul_hi(h & ~15, b << 12): a (fast) v_and instead of a (4-cycle) shift; the result is <= 255
-        const uint32_t B0 = ry.z, B1 = ry.w;
-        const int dx = 4 * grp;
-        uint32_t v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (__umulhi(h0[k] & ~15u, B0) + __umulhi(h1[k] & ~15u, B1) + 2) >> 2;
-        if (dx + 3 >= L.xvec) {  // FixedPtCast<int, uchar, 22> past the last SIMD block
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (dx + k >= L.xvec) v[k] = resize_tail(h0[k] * (B0 >> 12) + h1[k] * (B1 >> 12), L.area);
-        }
-        // pixels past L.w land in the row's pitch padding
-        *(uint32_t*)(dst + rr * L.pitch + dx) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-        rr += step_r;
-        grp += step_g;
-        if (grp >= ngrp) {
-            grp -= ngrp;
-            ++rr;
-        }
-    }
-}
-#endif
-
-// k_resize_rows: the same band, with the compute mapped so that a wave's row is uniform.  The block holds
-// R_s row sets of W_g waves (64 W_g >= the level's groups): lane (w % W_g) * 64 + lane of a set owns one
-// 4-pixel group for the whole band, its x selectors / weights in registers; set w / W_g takes rows
-// set, set + R_s, ...  A row's source-row LDS addresses and vertical weights come from scalar loads of the
-// y table, the store is a buffer store with the row offset in soffset: per 4 pixels only the taps, the
-// vertical rounding and the pack are VALU work (k_resize's per-item row / table LDS reads, index wrap
-// and 64-bit store address are gone).  Blocks of 256 <= 64 W_g R_s <= 512 threads (the host picks R_s).
+// k_resize_rows: one workgroup per band of LevelGeo::rs_rows output rows, the compute mapped so that a wave's
+// row is uniform.  The block holds R_s row sets of W_g waves (64 W_g >= the level's groups): lane
+// (w % W_g) * 64 + lane of a set owns one 4-pixel group for the whole band, its x selectors / weights in
+// registers; set w / W_g takes rows set, set + R_s, ...  A row's source-row LDS addresses and vertical
+// weights come from scalar loads of the y table, the store is a buffer store with the row offset in soffset:
+// per 4 pixels only the taps, the vertical rounding and the pack are VALU work.  Blocks of
+// 256 <= 64 W_g R_s <= 512 threads (the host picks R_s).
 template <bool MULTI>
 __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t* __restrict__ in, int64_t in_pitch,
                                                      uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
@@ -538,10 +421,7 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
 // from LDS, ping-ponging between two buffers (A: level 0 staging and even levels, B: odd levels).
 // tab: per (strip, level) int16 {computed lo, hi, owned lo, hi}; offB / offX: byte offsets of buffer B and
 // of the per-level x selector table in the dynamic LDS.
-#ifndef ORBFE_CASCADE_NT
-#define ORBFE_CASCADE_NT 1024
-#endif
-constexpr int kCasNT = ORBFE_CASCADE_NT;  // threads per strip workgroup
+constexpr int kCasNT = 1024;  // threads per strip workgroup
 __global__ __launch_bounds__(kCasNT) void k_resize_cascade(Geo g, const uint8_t* __restrict__ in, int64_t in_pitch,
                                                         uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
                                                         const ResizeY* __restrict__ yt, const int16_t* __restrict__ tab,
@@ -834,10 +714,7 @@ __device__ __forceinline__ int fd_minus_bit(int o, uint64_t m) {
 // cells per k_detect wavefront: 4 (the next cell's ROI loads overlap this one), or 1 for batches too small to
 // give the chip >= 8 waves per CU that way (a frame pair: 610 waves of 4 cells, 2 440 of one)
 constexpr int kFdCells = 4;
-#ifndef ORBFE_FD_SMALL_CELLS
-#define ORBFE_FD_SMALL_CELLS 1
-#endif
-constexpr int kFdSmallCells = ORBFE_FD_SMALL_CELLS;  // cells per wave for small batches (1 or 2)
+constexpr int kFdSmallCells = 1;  // cells per wave for small batches
 
 __device__ __forceinline__ int lanes_below(uint64_t b) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
@@ -850,12 +727,12 @@ __host__ __device__ inline int detect_roi_elems(const Geo& g, int rp) {
     return (n + 7) & ~7;
 }
 
-// V: 0 full kernel; ablations for tools/microbench.py: 1 ROI staging only, 2 + pre-test, 3 + M.
 // RP: ROI pitch in u16 (48, 64 or 96; >= widest ROI + 3).  NS: staged row slots (4 rows each, >= max_rh / 4).
-// 5 waves per SIMD (<= 96 VGPRs; 4 for the wider / taller ROI variants, which need the registers) and
+// CPW: cells per wave.  ST: the debug counters of orbfe_debug_detect_stats.
+// 5 waves per SIMD (<= 96 VGPRs; 4 for the wider / taller ROI shapes, which need the registers) and
 // <= 8 KiB of LDS for KITTI / EuRoC cells: detect is bound by how many
-// cells are in flight per CU (16 -> 10 resident waves costs +32 %, tools/microbench.py variant 8).
-template <int V, int RP, int NS, int CPW, bool ST = false>
+// cells are in flight per CU (16 -> 10 resident waves costs +32 %, measured by padding the launch's LDS).
+template <int RP, int NS, int CPW, bool ST = false>
 __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(Geo g, const CellGeo* __restrict__ cells, const uint8_t* __restrict__ in,
                                                int64_t in_pitch, const uint8_t* __restrict__ ws,
                                                int* __restrict__ cell_count, uint32_t* __restrict__ slots,
@@ -937,10 +814,6 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
         if (c + 1 < c_last) issue(c + 1);  // in flight during this cell's compute
         __syncthreads();
         auto process = [&]() {
-            if (V == 1) {  // ablation: ROI staging only
-                if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = roi[rw * rh / 2] & 0;
-                return;
-            }
             if (ww <= 0 || wh <= 0) {
                 if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = 0;
                 return;
@@ -1057,10 +930,6 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
             }
         }
         __syncthreads();
-        if (V == 2) {  // ablation: + pre-test / pair queue
-            if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = npq & 0;
-            return;
-        }
         // ---- 3. exact M of a queue's pairs -> M map; the pairs with a pixel above tl are compacted in place
         //         (entry i at qb[dir * i]: dir -1 for A at the back of pq) into the NMS queue; returns its length
         auto m_stage = [&](uint16_t* qb, int dir, int n, int tl) {
@@ -1140,10 +1009,6 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
         if (two && !collide) {
             int t0, t1;
             const int nna = m_stage(pq + cap - 1, -1, npa, max(tA, 1));
-            if (V == 3) {  // ablation: + exact M
-                if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = nna & 0;
-                return;
-            }
             nms_stage(pq + cap - 1, -1, nna, max(g.ini_th, 1), 0, t0, t1);
             total = t0;
             if (t0 == 0) {  // minTh fallback: every pair of B (the A pairs' M is recomputed, identically)
@@ -1157,10 +1022,6 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
             // straight out, minTh survivors are staged in the (dead) ROI area and copied out only if iniTh
             // kept nothing
             const int nnq = m_stage(pq, 1, npq, max(tq, 1));
-            if (V == 3) {  // ablation: + exact M
-                if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = nnq & 0;
-                return;
-            }
             const bool fb = g.min_th != g.ini_th;
             int t0, t1;
             nms_stage(pq, 1, nnq, max(g.ini_th, 1), fb ? max(g.min_th, 1) : 0, t0, t1);
@@ -1268,18 +1129,13 @@ __global__ __launch_bounds__(kOctThreads) void k_octree(Geo g, const CellGeo* __
                                                 const int* __restrict__ cell_count, const uint32_t* __restrict__ slots,
                                                 uint32_t* __restrict__ kd_all, uint16_t* __restrict__ kn_all,
                                                 uint32_t* __restrict__ lvl_kp, int* __restrict__ lvl_count,
-                                                int* __restrict__ overflow, int maxcell, int stop,
+                                                int* __restrict__ overflow, int maxcell,
                                                 long long* __restrict__ prof) {
-    // stop (tools/microbench.py ablations): 1 after the candidate gather, 2 after the initial columns,
-    // 3 after the full-division phase, 16 + l only level l, 64 + 8 l + n only level l and stop before
-    // pass n; 0 = the whole algorithm
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int scan_tmp[257];
     __shared__ int s_S, s_C, s_phase, s_cur, s_nexp, s_P, s_done;
     // grid (image, level): level-major dispatch, the long level-0 workgroups start first
     const int img = blockIdx.x, l = blockIdx.y, t = threadIdx.x;
-    if (stop >= 16 && stop < 64 && l != stop - 16) return;
-    if (stop >= 64 && l != (stop - 64) / 8) return;
     // prof (orbfe_debug_octree_profile): 64 wall-clock marks (100 MHz) per (image, level)
     long long* pm = prof ? prof + ((int64_t)img * g.nlevels + l) * 64 : nullptr;
     auto mark = [&](int id) {
@@ -1386,7 +1242,6 @@ __global__ __launch_bounds__(kOctThreads) void k_octree(Geo g, const CellGeo* __
             }
         }
         mark(1);
-        if (stop == 1) return;
         // 2. initial columns (:543-584); a key goes to column (size_t)(x / hX)
         const int nIni = L.n_ini;
         for (int i = t; i < 4 * NC; i += kOctThreads) d.cnt4[i] = 0;
@@ -1434,7 +1289,6 @@ __global__ __launch_bounds__(kOctThreads) void k_octree(Geo g, const CellGeo* __
         for (int k = t; k < K; k += kOctThreads) kn[k] = (uint16_t)d.cpos[kn[k]];
         __syncthreads();
         mark(2);
-        if (stop == 2) return;
 
         for (int iter = 0; !s_done; ++iter) {
             const int S = s_S, C = s_C, cur = s_cur, nxt = cur ^ 1;
@@ -1447,8 +1301,6 @@ __global__ __launch_bounds__(kOctThreads) void k_octree(Geo g, const CellGeo* __
                 __syncthreads();
                 break;
             }
-            if (stop == 3 && s_phase != 0) return;
-            if (stop >= 64 && iter == (stop - 64) % 8) return;
             mark(8 + 4 * iter);
             if (s_phase == 0) {
                 // ---------------- full pass (:605-664): divide every node holding more than one key
@@ -1701,10 +1553,7 @@ __global__ __launch_bounds__(kOctThreads) void k_octree(Geo g, const CellGeo* __
 // wave of the workgroup; the sweeps read the keys from a key-order copy the first sweep leaves in global
 // scratch.  Equal-size ties of the careful phase resolve by creation order, as in k_octree.
 constexpr int kObThreads = 256;
-#ifndef ORBFE_OB_BATCH
-#define ORBFE_OB_BATCH 4
-#endif
-constexpr int kObBatch = ORBFE_OB_BATCH;    // slot loads in flight per thread in the first sweep
+constexpr int kObBatch = 4;                 // slot loads in flight per thread in the first sweep
 constexpr uint32_t kObDeep = 0x80000000u;   // bin flag: holds nodes deeper than D0 (deep sweep / final map)
 // The node passes keep the list in wave 0's registers (kObNpl consecutive nodes per lane) when the level's
 // node capacity fits, i.e. max_ncap <= 64 kObNpl (every KITTI / EuRoC configuration up to ~3 900 features);
@@ -3258,9 +3107,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     auto stage = [&]() {
         wave_sync_lds();
         if (inside(cx)) commit();
-#ifndef ORBFE_X_ORB_NOBORDER  // ablation (wrong bits): border keypoints keep the previous window
         else stage_border(cx, cy);
-#endif
         wave_sync_lds();
     };
     auto prefetch = [&](int jn) {  // the loads of keypoint jn's window in flight from here
@@ -3347,12 +3194,6 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
                 uint32_t addr;
                 asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(xb >> 1), "s"(0xA0u), "v"((yb << 2) + kc));
                 lds_u32* p = (lds_u32*)(uintptr_t)addr;
-#ifdef ORBFE_X_ORB_PREBLURRED
-                // ablation (wrong bits; VERDICT r5 item 6's bound): a sample read as ONE byte of a window that
-                // would already be blurred (a blurred pyramid level) instead of the 7 vertical taps
-                v2[e] = *(const __attribute__((address_space(3))) uint8_t*)(uintptr_t)addr;
-                continue;
-#endif
                 const uint32_t p0 = p[0], p1 = p[kHDw], p2 = p[2 * kHDw], p3 = p[3 * kHDw];
                 const uint32_t sh = xb << 4;
                 uint32_t s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_alignbit(p1, p0, sh)), w2(18, 34), 32768u, false);
@@ -3387,9 +3228,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
         stage();
         const int ax = cx, ay = cy;
         if (has_b) prefetch(j + 1);
-#ifndef ORBFE_X_ORB_PREBLURRED  // (the ablation: no horizontal pass either)
         hpass();
-#endif
         int m10a, m01a, m10b = 0, m01b = 0;
         centroid(m10a, m01a);
         int bx = 0, by = 0;
@@ -3419,9 +3258,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
         record(j, ax, ay, angA, keyA);
         if (has_b) {
             wave_sync_lds();  // BRIEF A's hb reads are complete (waited before its ballots)
-#ifndef ORBFE_X_ORB_PREBLURRED
             hpass();
-#endif
             wave_sync_lds();  // hb complete
             brief(aB, bB, j + 1);
             record(j + 1, bx, by, angB, keyB);
@@ -3733,12 +3570,7 @@ __global__ __launch_bounds__(256) void k_stereo(Geo g, StereoArgs A) {
         int nx[kStU];
 #pragma unroll
         for (int j = 0; j < kStU; ++j) nx[j] = b + sl + 16 * j < e ? (int)bidxs[b + sl + 16 * j] : -1;
-#ifdef ORBFE_X_ST_NOSEARCH  // ablation (wrong results): no candidate loop, every keypoint matches right keypoint 0
-        key = 0u;
-        for (int k0 = e; k0 < e; k0 += 16 * kStU) {
-#else
         for (int k0 = b + sl; k0 < e; k0 += 16 * kStU) {
-#endif
             int iR[kStU];
 #pragma unroll
             for (int j = 0; j < kStU; ++j) iR[j] = nx[j];
@@ -3804,9 +3636,6 @@ __global__ __launch_bounds__(256) void k_stereo(Geo g, StereoArgs A) {
         // iniu < 0 or endu >= cols (:240-243); the slices stay inside the level otherwise
         do_sad = !(scaleduR0 < 0 || scaleduR0 + 11 >= lw) && scaledvL - 5 >= 0 && scaledvL + 6 <= lh &&
                  scaleduL - 5 >= 0 && scaleduL + 6 <= lw && scaleduR0 - 10 >= 0;
-#ifdef ORBFE_X_ST_NOSAD  // ablation (wrong results): no window staging, SAD or parabola
-        do_sad = false;
-#endif
         if (do_sad && sl < 11) {  // lane sl stages window row sl
             uint32_t wl[4], wr[6];
             wrow = scaledvL - 5 + sl;
@@ -4039,41 +3868,28 @@ __global__ __launch_bounds__(256) void k_hamming_search(const uint8_t* __restric
 
 // ------------------------------------------------------------------------------- launchers
 hipError_t launch_resize(const Geo& g, int l, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
-                         const ResizeY* yt, int n_images, hipStream_t s, int variant, int* zero_word) {
-    const LevelGeo& L = g.lv[l];  // LDS sized for this level (tables + its bands' source rows)
+                         const ResizeY* yt, int n_images, hipStream_t s, bool remainder_wave, int* zero_word) {
+    const LevelGeo& L = g.lv[l];  // LDS sized for this level (its bands' source rows)
     dim3 grid((L.h + L.rs_rows - 1) / L.rs_rows, n_images);
-    // production: k_resize_rows (profiles/r03/resize_rows_ab_r3f.log: 414 -> 394 us per 256 pairs
-    // standalone, +0.8 % on the 4-handle step); variants (tools/microbench.py): 4 = the item-mapped
-    // k_resize, 1 / 2 = its staging-only / compute-only ablations
-    if (variant == 0 || variant == 3 || variant == 5) {
-        // a level whose groups leave a last chunk of fewer than 40 (of 64) takes it in one remainder wave
-        // (variant 5: never, every chunk row-uniform); at most 8 waves per row set, each walking several
-        // chunks on rows wider than 2 048 px, so the block stays within __launch_bounds__(512)
-        const int ngrp = (L.w + 3) / 4, rem = ngrp % 64;
-        const int wg0 = (ngrp + 63) / 64;
-        const int remw = (variant != 5 && ngrp >= 64 && wg0 <= 8 && rem > 0 && rem < 40) ? 1 : 0;
-        const int wg = remw ? ngrp / 64 : wg0;
-        const int wgl = std::min(wg, 8 - remw);
-        const int sets = std::max(1, (4 - remw + wgl - 1) / wgl);  // >= 256 threads per block (the staging threads)
-        const int threads = 64 * (wgl * sets + remw);
-        if (threads < 256 || threads > 512) return hipErrorInvalidConfiguration;
-        // MULTI: a wave walks several 64-group chunks (levels wider than 2 048 px); the one-chunk form is
-        // instantiated apart (the loop around it cost 3 % on KITTI, tools/dbg/mb_ab.sh, round 4)
-        auto k = wg > wgl ? k_resize_rows<true> : k_resize_rows<false>;
-        hipLaunchKernelGGL(k, grid, dim3(threads), (size_t)L.rs_nsrc * L.rs_sp + 16, s, g, l, in, in_pitch, ws, xt, yt, wg,
-                           remw, wgl, zero_word);
-        return hipGetLastError();
-    }
-#ifdef ORBFE_DEV_VARIANTS
-    if (L.wide) return hipErrorInvalidValue;  // the round-2 kernel gathers every pixel from the group's 8 bytes
-    const size_t lds = (size_t)L.rs_ngrp * 36 + 16 * kRsRows + (size_t)L.rs_nsrc * L.rs_sp + 16;
-    if (L.rs_rows != kRsRows || lds > 150 * 1024) return hipErrorInvalidValue;  // kRsRows-row bands only
-    auto k = variant == 1 ? k_resize<1> : variant == 2 ? k_resize<2> : k_resize<0>;  // variant 4: k_resize<0>
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, s, g, l, in, in_pitch, ws, xt, yt);
+    // k_resize_rows against the round-2 item-mapped kernel (profiles/r03/resize_rows_ab_r3f.log): 414 -> 394 us
+    // per 256 pairs standalone, +0.8 % on the 4-handle step.
+    // a level whose groups leave a last chunk of fewer than 40 (of 64) takes it in one remainder wave
+    // (remainder_wave = false: never, every chunk row-uniform); at most 8 waves per row set, each walking several
+    // chunks on rows wider than 2 048 px, so the block stays within __launch_bounds__(512)
+    const int ngrp = (L.w + 3) / 4, rem = ngrp % 64;
+    const int wg0 = (ngrp + 63) / 64;
+    const int remw = (remainder_wave && ngrp >= 64 && wg0 <= 8 && rem > 0 && rem < 40) ? 1 : 0;
+    const int wg = remw ? ngrp / 64 : wg0;
+    const int wgl = std::min(wg, 8 - remw);
+    const int sets = std::max(1, (4 - remw + wgl - 1) / wgl);  // >= 256 threads per block (the staging threads)
+    const int threads = 64 * (wgl * sets + remw);
+    if (threads < 256 || threads > 512) return hipErrorInvalidConfiguration;
+    // MULTI: a wave walks several 64-group chunks (levels wider than 2 048 px); the one-chunk form is
+    // instantiated apart (the loop around it cost 3 % on KITTI, tools/dbg/mb_ab.sh, round 4)
+    auto k = wg > wgl ? k_resize_rows<true> : k_resize_rows<false>;
+    hipLaunchKernelGGL(k, grid, dim3(threads), (size_t)L.rs_nsrc * L.rs_sp + 16, s, g, l, in, in_pitch, ws, xt, yt, wg,
+                       remw, wgl, zero_word);
     return hipGetLastError();
-#else
-    return hipErrorInvalidValue;  // the microbench variants exist only in ORBFE_DEV_VARIANTS builds
-#endif
 }
 
 int detect_rp(const Geo& g) { return g.max_rw + 3 <= 48 ? 48 : g.max_rw + 3 <= 64 ? 64 : 96; }
@@ -4083,10 +3899,8 @@ size_t detect_lds_bytes(const Geo& g) {
     return 2 * (size_t)detect_roi_elems(g, detect_rp(g)) + (size_t)detect_rp(g) * (g.max_wh + 2) + 2 * (size_t)g.fd_pq;
 }
 
-// cells per wave for a batch: 4 unless that leaves fewer than 8 waves per CU (variant 4 / 1 force 4 / 1)
-int detect_cpw(const Geo& g, int n_images, int variant) {
-    if (variant == 4) return 4;
-    if (variant == 5) return 1;
+// cells per wave for a batch: 4 unless that leaves fewer than 8 waves per CU
+int detect_cpw(const Geo& g, int n_images) {
     // 8 pairs: 39 us with one cell per wave against 47 with four (tools/microbench.py, round 4)
     return n_images < kSmallBatchImages || (int64_t)n_images * ((g.ncells + kFdCells - 1) / kFdCells) < 8 * 256
                ? kFdSmallCells
@@ -4095,38 +3909,30 @@ int detect_cpw(const Geo& g, int n_images, int variant) {
 
 template <int RP, int NS>
 static void launch_detect_rp(const Geo& g, const CellGeo* cells, const uint8_t* in, int64_t in_pitch, const uint8_t* ws,
-                             int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int variant, int* stats) {
-    const int cpw = detect_cpw(g, n_images, variant);
+                             int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int cpw, int* stats) {
     const dim3 grid((g.ncells + cpw - 1) / cpw, n_images), blk(64);
-#ifdef ORBFE_DEV_VARIANTS
-    // variants 8 / 9: the full kernel with 6 / 12 KiB of extra (unused) LDS, to measure how detect
-    // time depends on occupancy; 1 / 2 / 3: the ablations (tools/microbench.py)
-    const size_t lds = detect_lds_bytes(g) + (variant == 8 ? 6144 : variant == 9 ? 12288 : 0);
-    auto k = variant == 1 ? k_detect<1, RP, NS, kFdCells> : variant == 2 ? k_detect<2, RP, NS, kFdCells>
-           : variant == 3 ? k_detect<3, RP, NS, kFdCells> : cpw == 1 ? k_detect<0, RP, NS, 1>
-           : cpw == kFdSmallCells ? k_detect<0, RP, NS, kFdSmallCells> : k_detect<0, RP, NS, kFdCells>;
-#else
     const size_t lds = detect_lds_bytes(g);
-    auto k = stats ? (cpw == kFdSmallCells ? k_detect<0, RP, NS, kFdSmallCells, true> : k_detect<0, RP, NS, kFdCells, true>)  // debug counters
-                   : (cpw == kFdSmallCells ? k_detect<0, RP, NS, kFdSmallCells> : k_detect<0, RP, NS, kFdCells>);
-#endif
+    auto k = stats ? (cpw == kFdSmallCells ? k_detect<RP, NS, kFdSmallCells, true> : k_detect<RP, NS, kFdCells, true>)  // debug counters
+                   : (cpw == kFdSmallCells ? k_detect<RP, NS, kFdSmallCells> : k_detect<RP, NS, kFdCells>);
     hipLaunchKernelGGL(k, grid, blk, lds, s, g, cells, in, in_pitch, ws, cell_count, slots, stats);
 }
 
 hipError_t launch_detect(const Geo& g, const CellGeo* cells, const uint8_t* in, int64_t in_pitch, const uint8_t* ws,
-                         int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int variant, int* stats) {
+                         int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int cells_per_wave, int* stats) {
+    const int cpw = cells_per_wave ? cells_per_wave : detect_cpw(g, n_images);
+    if (cpw != kFdCells && cpw != kFdSmallCells) return hipErrorInvalidValue;
     // ROIs of at most 48 rows (KITTI, EuRoC) stage from 12 registers, taller ones (<= 64) from 16
     const bool tall = g.max_rh > 48;
     switch (detect_rp(g)) {
         case 48:
-            if (tall) launch_detect_rp<48, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, variant, stats);
-            else launch_detect_rp<48, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, variant, stats);
+            if (tall) launch_detect_rp<48, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
+            else launch_detect_rp<48, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
             break;
         case 64:
-            if (tall) launch_detect_rp<64, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, variant, stats);
-            else launch_detect_rp<64, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, variant, stats);
+            if (tall) launch_detect_rp<64, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
+            else launch_detect_rp<64, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
             break;
-        default: launch_detect_rp<96, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, variant, stats);
+        default: launch_detect_rp<96, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
     }
     return hipGetLastError();
 }
@@ -4191,13 +3997,10 @@ static int lds_limit(const void* fn) {
 
 hipError_t prepare_resize_cascade(int lds_bytes) { return raise_lds((const void*)k_resize_cascade, lds_bytes); }
 
-#ifndef ORBFE_OB_SMALL_NT
-#define ORBFE_OB_SMALL_NT 512
-#endif
 // k_octree_bins threads for small batches: 512 (8 pairs: 35.5 -> 33.1 us against 1 024 — the passes run on
 // <= 512 list positions, so waves 8-15 only added issue contention; level 0's key sweep is slower, but the
 // kernel's critical path is a small level's careful iterations; tools/octree_profile.py, round 5)
-constexpr int kObSmallNT = ORBFE_OB_SMALL_NT;
+constexpr int kObSmallNT = 512;
 static const void* octree_bins_fn(const Geo& g, bool wide) {
     const bool reg = octree_reg_passes(g.max_ncap);
     return wide ? (reg ? (const void*)k_octree_bins<kObSmallNT, true> : (const void*)k_octree_bins<kObSmallNT, false>)
@@ -4227,11 +4030,12 @@ hipError_t launch_resize_cascade(const Geo& g, const uint8_t* in, int64_t in_pit
 
 hipError_t launch_octree(const Geo& g, const CellGeo* cells, const int* cell_count, const uint32_t* slots,
                          const uint32_t* octab, uint32_t* kd, uint16_t* kn, uint32_t* lvl_kp, int* lvl_count, int* overflow,
-                         int maxcell, int n_images, hipStream_t s, int variant, long long* prof) {
+                         int maxcell, int n_images, hipStream_t s, int threads, long long* prof) {
     if (g.oct_v == 0) {
         const size_t lds = octree_bins_lds_bytes(g, maxcell);
-        // kObSmallNT threads for small batches (variant 1 / 2 force 256 / kObSmallNT, tools/microbench.py)
-        const bool wide = variant == 2 || (variant != 1 && n_images < kSmallBatchImages);
+        // kObSmallNT threads for small batches, kObThreads otherwise
+        if (threads != 0 && threads != kObThreads && threads != kObSmallNT) return hipErrorInvalidValue;
+        const bool wide = threads ? threads == kObSmallNT : n_images < kSmallBatchImages;
         const void* fn = octree_bins_fn(g, wide);
         if ((int)lds > lds_limit(fn)) return hipErrorInvalidConfiguration;  // prepare_octree
         const bool reg = octree_reg_passes(g.max_ncap);
@@ -4241,10 +4045,11 @@ hipError_t launch_octree(const Geo& g, const CellGeo* cells, const int* cell_cou
                            slots, octab, lvl_kp, lvl_count, overflow, maxcell, kd, prof);
         return hipGetLastError();
     }
+    if (threads != 0) return hipErrorInvalidValue;  // k_octree has one shape (kOctThreads)
     const size_t lds = octree_lds_bytes(g, maxcell);
     if ((int)lds > lds_limit((const void*)k_octree)) return hipErrorInvalidConfiguration;
     hipLaunchKernelGGL(k_octree, dim3(n_images, g.nlevels), dim3(kOctThreads), lds, s, g, cells, cell_count, slots, kd, kn,
-                       lvl_kp, lvl_count, overflow, maxcell, variant, prof);
+                       lvl_kp, lvl_count, overflow, maxcell, prof);
     return hipGetLastError();
 }
 
@@ -4268,17 +4073,11 @@ static void launch_orb_nw(const Geo& g, const uint8_t* in, int64_t in_pitch, con
 // k_orb can carry the stereo buckets when the (H + 1) counters fit its s_h buffer (256-thread workgroups)
 bool orb_fuses_bucket(const Geo& g) { return g.H + 1 <= 4 * kHPairs * kHDw; }
 
-#ifndef ORBFE_ORB_SMALL_KPW
-#define ORBFE_ORB_SMALL_KPW 2
-#endif
-constexpr int kOrbSmallKpw = ORBFE_ORB_SMALL_KPW;  // keypoints per wave below the 4-keypoint threshold (2 or 4)
+constexpr int kOrbSmallKpw = 2;  // keypoints per wave below the 4-keypoint threshold
 // keypoints per wave for a batch: 8 (4 waves per workgroup: 953 -> 914 us per 256 pairs against 4, same-box
 // A/B, round 1) while the batch gives >= 16 waves per CU that way, else 4, else 2 (a frame pair: 508 waves of
-// 8 keypoints, 2 028 of 2).  Variants (microbench): 1 / 9 / 2 force 8 / 4 / 2.
-int orb_kpw(const Geo& g, int n_images, int variant) {
-    if (variant == 1) return 8;
-    if (variant == 9) return 4;
-    if (variant == 2 || variant == 12) return 2;
+// 8 keypoints, 2 028 of 2).
+int orb_kpw(const Geo& g, int n_images) {
     for (int k : {8, 4})
         if ((int64_t)orb_waves(g, k) * n_images >= 16 * 256) return k;
     return kOrbSmallKpw;
@@ -4286,26 +4085,16 @@ int orb_kpw(const Geo& g, int n_images, int variant) {
 
 hipError_t launch_orb(const Geo& g, const uint8_t* in, int64_t in_pitch, const uint8_t* ws, const uint32_t* lvl_kp,
                       const int* lvl_count, orbfe_keypoint* out_kp, uint8_t* out_desc, int* out_count, int n_images,
-                      const uint32_t* tab, hipStream_t s, int variant, const StereoArgs* bucket, int n_bucket) {
+                      const uint32_t* tab, hipStream_t s, int keypoints_per_wave, const StereoArgs* bucket, int n_bucket) {
     if (bucket && !orb_fuses_bucket(g)) return hipErrorInvalidValue;
-#ifdef ORBFE_DEV_VARIANTS
-    if (variant == 8) {
-        launch_orb_nw<8, 4>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s, nullptr, 0);
-        return hipGetLastError();
-    }
-    if (variant == 10) {
-        launch_orb_nw<4, 16>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s, bucket,
-                             n_bucket);
-        return hipGetLastError();
-    }
-#endif
-    switch (orb_kpw(g, n_images, variant)) {
+    switch (keypoints_per_wave ? keypoints_per_wave : orb_kpw(g, n_images)) {
         case 2: launch_orb_nw<4, 2>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s,
                                     bucket, n_bucket); break;
         case 4: launch_orb_nw<4, 4>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s,
                                     bucket, n_bucket); break;
-        default: launch_orb_nw<4, 8>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s,
-                                     bucket, n_bucket);
+        case 8: launch_orb_nw<4, 8>(g, in, in_pitch, ws, lvl_kp, lvl_count, out_kp, out_desc, out_count, n_images, tab, s,
+                                    bucket, n_bucket); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -339,3 +339,49 @@ def test_deep_octree_nodes_batch_and_single():
         assert kps.tobytes() == okps.tobytes() and np.array_equal(desc, odesc), f"batch image {i}"
         k1, d1 = ex.extract(imgs[i])
         assert k1.tobytes() == okps.tobytes() and np.array_equal(d1, odesc), f"single image {i}"
+
+
+def test_forced_launch_shapes_leave_the_same_bits():
+    """orbfe_microbench's surviving non-zero variants of detect, octree and describe (the table in orbfe.h)
+    force cells per wave, octree threads and keypoints per wave away from the automatic choice.  Each one
+    re-runs its stage on the batch's own buffers; the later stages are then re-run in their automatic shape
+    (variant 0), so that what the forced shape wrote is what they read, and the fetched keypoints,
+    descriptors and stereo result are compared with the oracle and with the batch's own stereo result after
+    every forced variant (for a batch of two images the automatic shapes are one cell per wave, 512 octree
+    threads and two keypoints per wave: variants 1:4, 2:1, 3:1 and 3:9 run shapes the batch did not).  The
+    smallest geometry of this file (8 levels, single-cell top levels).  A removed number of every stage is
+    refused with ORBFE_EINVAL."""
+    torch = pytest.importorskip("torch")
+    from pyorbslam_amd._lib import ORBFE_EINVAL, OrbfeError
+    from pyorbslam_amd.batch import StereoFrontEnd
+    w, h = 211, 157
+    params = dict(KITTI, nfeatures=500)
+    pair = np.stack(synth.make_pair(31, w, h))
+    oracle = [O.OracleExtractor(**params).extract(pair[i]) for i in range(2)]
+    fe = StereoFrontEnd(width=w, height=h, max_pairs=1, nfeatures=500)
+    fe.enqueue(torch.from_numpy(pair).cuda(), 1)
+    assert fe.overflow() == 0
+    stereo0 = fe.fetch_stereo(0)
+    assert int((stereo0["status"] > 0).sum()) > 0
+    ms = C.c_float()
+
+    def check(what):
+        assert fe.overflow() == 0, what
+        for i, (okps, odesc) in enumerate(oracle):
+            kps, desc = fe.fetch_image(i)
+            assert len(kps) == len(okps) > 0, (what, i)
+            assert kps.tobytes() == okps.tobytes() and np.array_equal(desc, odesc), (what, i)
+        stereo1 = fe.fetch_stereo(0)
+        assert sorted(stereo0) == sorted(stereo1), what
+        assert all(np.array_equal(stereo0[k], stereo1[k]) for k in stereo0), what
+
+    check("batch")
+    for stage, variant in [(1, 4), (1, 5), (2, 1), (2, 2), (3, 1), (3, 9), (3, 2), (3, 12)]:
+        call("orbfe_microbench", fe.handle, stage, variant, 1, C.byref(ms))
+        for later in range(stage + 1, 5):
+            call("orbfe_microbench", fe.handle, later, 0, 1, C.byref(ms))
+        check((stage, variant))
+    for stage, variant in [(0, 3), (0, 100), (0, 100000), (1, 2), (2, 16), (3, 8), (4, 1), (5, 0), (1, -1)]:
+        with pytest.raises(OrbfeError) as e:
+            call("orbfe_microbench", fe.handle, stage, variant, 1, C.byref(ms))
+        assert e.value.code == ORBFE_EINVAL, (stage, variant)

@@ -1,8 +1,9 @@
-"""Sweep of a per-handle tuning variable read when a handle is created or reserved (ORBFE_PRIO: wave
-priorities r,d,o,k,b,s; ORBFE_STAGE_REPEAT: launches per stage r,d,o,k,s; ORBFE_OCT_KEYS ...) on the default
-4-handle bench step, one process, configurations interleaved over several rounds.
-usage: python tools/dbg/env_sweep.py [--var ORBFE_PRIO] [--rounds 3] CFG [CFG ...]
-       CFG: digits joined with commas (002000 -> "0,0,2,0,0,0"), or any string after "=" (=7424)"""
+"""Step timer: the default 4-handle bench step in one process, pairs/s per round (tools/dbg/ab.sh and
+stage_ab.sh call it with one dummy configuration, "=0").  It began as a sweep of per-handle tuning variables;
+the library reads no environment variable any more, so --var / CFG only label the rounds: each CFG is set
+as the value of --var before the handles are created and the rounds of the CFGs are interleaved.
+usage: python tools/dbg/env_sweep.py [--var NAME] [--rounds 3] CFG [CFG ...]
+       CFG: digits joined with commas (002000 -> "0,0,2,0,0,0"), or any string after "=" (=0)"""
 import argparse
 import os
 import sys
@@ -15,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--var", default="ORBFE_PRIO")
+    ap.add_argument("--var", default="ORBFE_NONE")
     ap.add_argument("--pairs", type=int, default=512)
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--steps", type=int, default=20)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ stall / issue counters of one stage standalone (tools/microbench.py STAGE:0, 256 pairs), in-tree library
-# and optionally a variant: bash tools/dbg/pmc_stage.sh STAGE OUTNAME [VARIANT]
+# and optionally that of another revision (tools/build_rev.sh REV): bash tools/dbg/pmc_stage.sh STAGE OUTNAME [REV]
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 st=$1; name=$2; var=$3

@@ -1,4 +1,6 @@
-"""Per-kernel micro-benchmark / ablation on one resident batch (development aid).
+"""Per-kernel micro-benchmark on one resident batch (development aid): each stage standalone, in the automatic
+launch shape (variant 0) or a forced one.  The stages and their variant numbers are the table at
+orbfe_microbench in include/orbfe.h; every variant leaves the stage's correct outputs behind.
 usage: python tools/microbench.py [--pairs 64] [--rounds 3] stage:variant ...   (stage 0 resize .. 4 stereo)"""
 import argparse
 import ctypes as C
@@ -31,9 +33,8 @@ def main():
             ms = C.c_float()
             call("orbfe_microbench", fe.handle, st, var, a.reps, C.byref(ms))
             res[it].append(round(ms.value * 1000, 1))
-            fe.enqueue(imgs)  # restore real stage outputs for the next item
             torch.cuda.synchronize()
-    names = ["resize", "detect", "octree", "describe", "stereo", "blurwrite"]
+    names = ["resize", "detect", "octree", "describe", "stereo"]
     for it, v in res.items():
         st, var = map(int, it.split(":"))
         print(f"{names[st]:9s} v{var}: us per launch {v}  (min {min(v)})")
