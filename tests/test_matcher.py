@@ -83,6 +83,66 @@ def test_hamming_search_top2_matches_sequential_scan():
         assert (bd[k], bi[k], sd[k], si[k]) == (b1, i1, b2, i2), k
 
 
+def _sequential_top2(q, t, cand):
+    """The reference's best / second scan (ORBMatcher.py:258-274) over one candidate list."""
+    b1, i1, b2, i2 = 256, -1, 256, -1
+    for c in cand:
+        d = MO.dist(q, t[c])
+        if d < b1:
+            b2, i2, b1, i1 = b1, i1, d, int(c)
+        elif d < b2:
+            b2, i2 = d, int(c)
+    return b1, i1, b2, i2
+
+
+@pytest.mark.gpu
+def test_hamming_search_list_length_tails():
+    """k_hamming_search at its edges: 301 queries (four per block, so the last block holds one), candidate
+    lists of 0, 1, 2 and around one and two passes of the 64 lanes, one query whose candidates are all the same
+    descriptor (only the position separates best from second, through every step of the wave's merge), and one
+    whose only candidates lie at the largest distance, 256, which the sequential `d < best` never accepts."""
+    from pyorbslam_amd import matcher
+    from pyorbslam_amd._lib import call, ptr
+    nq, nt = 301, 700
+    rng = np.random.default_rng(11)
+    q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+    t[::5] = t[1]  # duplicates: equal distances at different positions
+    t[7] = ~q[298]
+    tails = [0, 1, 2, 63, 64, 65, 127, 128, 129]
+    lens = np.array([tails[k % len(tails)] for k in range(nq)])
+    lens[300] = 129  # the one query of the last block
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    idx = rng.integers(0, nt, off[-1]).astype(np.int32)
+    assert lens[299] == 2 and lens[298] == 1 and lens[296] == 129
+    idx[off[296]:off[297]] = np.where(np.arange(129) % 2, 5, 10)  # t[5] == t[10] == t[1]: one descriptor
+    idx[off[298]] = 7                                             # distance 256
+    bd, bi, sd, si = (np.full(nq, -7, np.int32) for _ in range(4))
+    call("orbfe_hamming_search", matcher._h(), ptr(q), nq, ptr(t), nt, ptr(off), ptr(idx), ptr(bd), ptr(bi), ptr(sd),
+         ptr(si))
+    for k in range(nq):
+        want = _sequential_top2(q[k], t, idx[off[k]:off[k + 1]])
+        assert (bd[k], bi[k], sd[k], si[k]) == want, (k, int(lens[k]))
+    assert (bi[296], si[296]) == (10, 5) and bd[296] == sd[296]
+    assert (bd[298], bi[298], sd[298], si[298]) == (256, -1, 256, -1)
+    assert (bd[0], bi[0], sd[0], si[0]) == (256, -1, 256, -1) and bi[1] == idx[off[1]] and si[1] == -1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [255, 256, 257])
+def test_hamming_matrix_row_tails(nb):
+    """k_hamming_matrix with rows one short of, equal to and one past its 256-thread block."""
+    from pyorbslam_amd.matcher import hamming_matrix
+    rng = np.random.default_rng(nb)
+    a = rng.integers(0, 256, (5, 32), dtype=np.uint8)
+    b = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+    b[-1], b[0] = a[4], ~a[0]
+    lut = np.array([bin(i).count("1") for i in range(256)], np.int32)
+    got = hamming_matrix(a, b)
+    assert got.shape == (5, nb) and np.array_equal(got, lut[a[:, None, :] ^ b[None, :, :]].sum(2))
+    assert got[4, -1] == 0 and got[0, 0] == 256
+
+
 @pytest.mark.gpu
 def test_hamming_concurrent_threads():
     """ORBMatcher / MapPoint are called from the Tracking, LocalMapping and LoopClosing threads at once
