@@ -22,6 +22,7 @@ GOLD = ROOT / "tests" / "golden"
 sys.path.insert(0, str(ROOT / "tests"))
 sys.path.insert(0, "/root/reference")
 
+import bow_cases as BC  # noqa: E402
 import vocab_synth as VS  # noqa: E402
 from pyDBoW.TemplatedVocabulary import TemplatedVocabulary  # noqa: E402
 
@@ -30,13 +31,20 @@ CASES = [
     ("k5L3", dict(seed=1, k=5, L=3), 11, 300, (2, 4)),            # System.py:38 configuration
     ("k10L4_ragged", dict(seed=2, k=10, L=4, p_stop=0.25, p_dup=0.1, p_zero=0.1, order="dfs"), 12, 600, (1, 2, 4)),
     ("k20L2_ties", dict(seed=3, k=20, L=2, p_dup=0.4, p_zero=0.05), 13, 300, (1, 3)),
+    # nodes of up to 300 children under the header k = 10 (the loader checks the header, never a node's fan-out):
+    # tests/bow_cases.py; the queries are every leaf's descriptor (query seed 14)
+    ("wide", None, 14, None, (0, 1, 2)),
 ]
 
 
 def main():
     for name, kw, qseed, nq, lups in CASES:
-        tree = VS.make_tree(**kw)
-        q = VS.query_descriptors(tree, qseed, nq)
+        if name == "wide":
+            tree = BC.wide_tree(BC.WIDE_SEED)
+            q, q_node = BC.leaf_queries(tree, qseed)
+        else:
+            tree = VS.make_tree(**kw)
+            q = VS.query_descriptors(tree, qseed, nq)
         with tempfile.TemporaryDirectory() as td:
             path = Path(td) / "voc.txt"
             VS.write_text(tree, path)
@@ -53,6 +61,9 @@ def main():
             out[f"fv_idx_{lu}"] = np.array([i for v in fv.values() for i in v], np.int64)
             out[f"bv_type_{lu}"] = type(bv).__name__
             print(name, "levels_up", lu, "words", len(bv), "nodes", len(fv))
+        if name == "wide":  # the queries are node descriptors: their node ids keep the fixture at half the size
+            del out["queries"]
+            out["query_node"] = q_node.astype(np.int32)
         np.savez_compressed(GOLD / f"vocab_{name}.npz", **out)
     # header outside the accepted ranges: load_from_text_file prints and returns False
     with tempfile.TemporaryDirectory() as td:
