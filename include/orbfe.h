@@ -32,8 +32,10 @@ extern "C" {
 /* ABI revision of this header (orbfe_abi_version() returns the library's).  4: ORBFE_NSTAGES = 5 (stage 3
  * describe, 4 stereo; the round-1 blur stage and orbfe_set_blur_fork are gone), orbfe_set_graphs,
  * orbfe_set_octree_kernel / orbfe_get_octree_kernel, orbfe_debug_detect_stats. */
-#define ORBFE_ABI_VERSION 7 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
-                               * sides above 4 095 px are accepted (kKeyXYBits).  7: orbfe_kfdb_*, orbfe_bow_score */
+#define ORBFE_ABI_VERSION 8 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
+                               * sides above 4 095 px are accepted (kKeyXYBits).  7: orbfe_kfdb_*, orbfe_bow_score.
+                               * 8: orbfe_vocab_bow, orbfe_vocab_bow_device, orbfe_vocab_bow_scratch_bytes,
+                               * orbfe_vocab_bow_last_ms (additive) */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -431,6 +433,61 @@ int orbfe_vocab_transform_device(orbfe_vocab_handle v, const uint8_t* d_desc32, 
                                  int32_t* d_word_id, int32_t* d_node_id, double* d_weight, void* hip_stream);
 /* Kernel time of the last orbfe_vocab_transform (ms, HIP events), for measurement. */
 int orbfe_vocab_last_ms(orbfe_vocab_handle v, float* ms);
+
+/* BowVector and FeatureVector of whole frames, assembled on the device (TemplatedVocabulary.transform,
+ * TemplatedVocabulary.py:108-129; BowVector.py:8-28; FeatureVector.py:8-19): k_vocab_descend, then k_bow_assemble
+ * with one workgroup per frame, on one stream.  Per frame, with features i = 0 .. n - 1 in order:
+ *   - nid_i is the node feature i's descent entered at depth nid_level, else nid_(i-1), with nid_(-1) = 0;
+ *     the threading runs over every feature of the frame and restarts with every frame;
+ *   - feature i is kept iff its weight > 0 (zero, negative and NaN weights drop it from both vectors);
+ *   - BoW vector: the distinct word ids of the kept features, ascending; a word's raw weight is the sum of its
+ *     kept features' weights in ascending feature index, sequentially, in IEEE double; total is the sum of the
+ *     raw weights in ascending word id, sequentially, in IEEE double; when total > 0 every weight is raw / total;
+ *   - feature vector: the distinct nid of the kept features, ascending, each with its kept feature indices
+ *     ascending, as CSR: node r's indices are fv_idx[fv_end[r - 1] .. fv_end[r]) (fv_end[-1] = 0).
+ * ORBFE_BOW_MAX_FRAME is the longest frame the kernel takes (its keys stay in LDS). */
+#define ORBFE_BOW_MAX_FRAME 8192
+/* Caller-owned output arrays: one entry per frame in n_words / n_nodes / n_kept, and per frame a block of
+ * entries in the others (where the block starts and how long it is: see the two entry points).  Entries past a
+ * frame's n_words (bow_*), n_nodes (fv_node, fv_end) and n_kept (fv_idx) are unspecified. */
+typedef struct orbfe_bow_out {
+    int32_t* n_words;   /* distinct words of the frame                                  */
+    int32_t* bow_word;  /* word ids, ascending                                          */
+    double* bow_weight; /* their normalised weights                                     */
+    int32_t* n_nodes;   /* distinct nodes of the frame                                  */
+    int32_t* fv_node;   /* node ids, ascending                                          */
+    int32_t* fv_end;    /* exclusive end of each node's run in fv_idx                   */
+    int32_t* fv_idx;    /* kept feature indices grouped by node, ascending in a run     */
+    int32_t* n_kept;    /* kept features of the frame = entries of fv_idx               */
+    int32_t* status;    /* ONE word: the OR of the ORBFE_BOW_* flags below over all frames (the caller zeroes
+                         * it); may be NULL for orbfe_vocab_bow, which clamps nothing     */
+} orbfe_bow_out;
+#define ORBFE_BOW_OVER_OUT 1   /* a count above out_stride was clamped to it            */
+#define ORBFE_BOW_OVER_MAX 2   /* a count above ORBFE_BOW_MAX_FRAME was clamped to it   */
+#define ORBFE_BOW_OVER_FRAME 4 /* a count above frame_stride was clamped to it          */
+#define ORBFE_BOW_NEGATIVE 8   /* a negative count was taken as 0                       */
+/* Device pointers, enqueued on hip_stream (void* = hipStream_t) without synchronising and without allocating.
+ * Frame f < n_frames is the d_count[f * count_stride] descriptors that start at descriptor f * frame_stride of
+ * d_desc32 (16-byte aligned, as for orbfe_vocab_transform_device; ORBFE_EINVAL before any launch otherwise); the
+ * counts are read on the device.  Frame f's outputs start at entry f * out_stride of the per-entry arrays of
+ * *d_out (a host struct of device pointers).  A count that is negative or above out_stride, ORBFE_BOW_MAX_FRAME
+ * or frame_stride is clamped and flagged in *d_out->status; nothing is read or written past the clamped length.
+ * d_scratch: 8-byte aligned device memory of at least orbfe_vocab_bow_scratch_bytes bytes, free for reuse once
+ * the work on hip_stream is done.  n_frames = 0 launches nothing.  With frame_stride = 2 * kp_cap and
+ * count_stride = 2 on an orbfe_batch_view's desc / count this takes a stereo batch's left images. */
+int orbfe_vocab_bow_device(orbfe_vocab_handle v, const uint8_t* d_desc32, int64_t frame_stride,
+                           const int32_t* d_count, int64_t count_stride, int32_t n_frames, int32_t nid_level,
+                           int64_t out_stride, const orbfe_bow_out* d_out, void* d_scratch, int64_t scratch_bytes,
+                           void* hip_stream);
+int orbfe_vocab_bow_scratch_bytes(int32_t n_frames, int64_t frame_stride, int64_t* bytes);
+/* The same over host buffers, synchronous: frame f is descriptors [off[f], off[f + 1]) of desc32 (off[0] = 0,
+ * non-decreasing) and its outputs are packed at entry off[f] of the per-entry arrays (off[n_frames] entries each).
+ * ORBFE_EINVAL when a frame is longer than ORBFE_BOW_MAX_FRAME.  The vocabulary's own buffers, stream and events,
+ * serialised among threads like orbfe_vocab_transform. */
+int orbfe_vocab_bow(orbfe_vocab_handle v, const uint8_t* desc32, const int64_t* off, int32_t n_frames,
+                    int32_t nid_level, const orbfe_bow_out* out);
+/* Kernel time of the last orbfe_vocab_bow (descent + assembly, ms, HIP events), for measurement. */
+int orbfe_vocab_bow_last_ms(orbfe_vocab_handle v, float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

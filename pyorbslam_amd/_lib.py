@@ -40,6 +40,18 @@ class VocabInfo(C.Structure):
                 ("n_nodes", C.c_int64), ("n_words", C.c_int64), ("depth", C.c_int32), ("max_children", C.c_int32)]
 
 
+ORBFE_ABI_VERSION = 8
+ORBFE_BOW_MAX_FRAME = 8192  # the longest frame k_bow_assemble takes (include/orbfe.h)
+# flags of BowOut.status
+ORBFE_BOW_OVER_OUT, ORBFE_BOW_OVER_MAX, ORBFE_BOW_OVER_FRAME, ORBFE_BOW_NEGATIVE = 1, 2, 4, 8
+
+
+class BowOut(C.Structure):
+    """orbfe_bow_out: caller-owned output arrays of orbfe_vocab_bow / orbfe_vocab_bow_device."""
+    _fields_ = [(k, C.c_void_p) for k in ("n_words", "bow_word", "bow_weight", "n_nodes", "fv_node", "fv_end",
+                                          "fv_idx", "n_kept", "status")]
+
+
 # cv::KeyPoint tuple layout (opencv_type_casters.h:106-108)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4")])
@@ -119,6 +131,11 @@ SIGNATURES = {
     "orbfe_vocab_transform_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p],
     "orbfe_vocab_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
+    "orbfe_vocab_bow_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                               C.c_int64, C.POINTER(BowOut), C.c_void_p, C.c_int64, C.c_void_p],
+    "orbfe_vocab_bow_scratch_bytes": [C.c_int32, C.c_int64, C.POINTER(C.c_int64)],
+    "orbfe_vocab_bow": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BowOut)],
+    "orbfe_vocab_bow_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
     "orbfe_kfdb_create": [C.c_int64, C.c_int64, C.POINTER(C.c_void_p)],
     "orbfe_kfdb_destroy": [C.c_void_p],
     "orbfe_kfdb_add": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BatchView, call, ptr
+from ._lib import KP_DTYPE, BatchView, BowOut, call, ptr
 
 KITTI_BF = 386.1448  # KITTI00-02.yaml Camera.bf
 KITTI_FX = 718.856   # KITTI00-02.yaml Camera.fx
@@ -46,6 +46,7 @@ class StereoFrontEnd:
         v = BatchView()
         call("orbfe_batch_view_get", h, C.byref(v))
         self.kp_cap = v.kp_cap
+        self._bow, self._bow_frames = None, 0  # bow()'s device buffers, made on its first call
         self.scales = np.zeros(int(nlevels), np.float32)  # the level scale factors (compact records)
         call("orbfe_get_scales", h, self.scales.ctypes.data_as(C.c_void_p), None, None, None, None)
 
@@ -91,6 +92,62 @@ class StereoFrontEnd:
         v = C.c_int32()
         call("orbfe_batch_status", self._h, C.byref(v))
         return v.value
+
+    def bow(self, vocab, levels_up: int = 4, side: str = "left", stream_ptr: int = 0) -> int:
+        """Enqueue the BoW and feature vectors of the last batch's images on stream_ptr (the stream the batch was
+        enqueued on): orbfe_vocab_bow_device on the batch view's desc / count, nothing goes through the host.
+        side="left": frame p is pair p's left image; "both": frame i is image i.  Returns the number of frames;
+        fetch_bow(i) reads one.  Output and scratch buffers are allocated on the first call and kept."""
+        import torch
+        if side not in ("left", "both"):
+            raise ValueError('side must be "left" or "both"')
+        v = BatchView()
+        call("orbfe_batch_view_get", self._h, C.byref(v))
+        step = 2 if side == "left" else 1
+        n_frames = v.n_images // step
+        cap = self.kp_cap
+        if self._bow is None:
+            m = 2 * self.max_pairs
+            need = C.c_int64()
+            call("orbfe_vocab_bow_scratch_bytes", m, 2 * cap, C.byref(need))
+            dev = torch.device("cuda", torch.cuda.current_device())
+            ints = torch.zeros((4, m, cap), dtype=torch.int32, device=dev)    # bow_word, fv_node, fv_end, fv_idx
+            per = torch.zeros((4, m), dtype=torch.int32, device=dev)          # n_words, n_nodes, n_kept, status
+            weight = torch.zeros((m, cap), dtype=torch.float64, device=dev)
+            scratch = torch.zeros(max(need.value, 8) // 8, dtype=torch.int64, device=dev)
+            out = BowOut(n_words=per[0].data_ptr(), bow_word=ints[0].data_ptr(), bow_weight=weight.data_ptr(),
+                         n_nodes=per[1].data_ptr(), fv_node=ints[1].data_ptr(), fv_end=ints[2].data_ptr(),
+                         fv_idx=ints[3].data_ptr(), n_kept=per[2].data_ptr(), status=per[3].data_ptr())
+            torch.cuda.synchronize()  # once: the fills above ran on torch's stream, the kernels run on stream_ptr
+            self._bow = dict(ints=ints, per=per, weight=weight, scratch=scratch, out=out)
+        b = self._bow
+        self._bow_frames = n_frames
+        if n_frames:
+            call("orbfe_vocab_bow_device", vocab._handle(), C.c_void_p(v.desc), step * cap, C.c_void_p(v.count), step,
+                 n_frames, int(vocab.L - levels_up), cap, C.byref(b["out"]), C.c_void_p(b["scratch"].data_ptr()),
+                 b["scratch"].numel() * 8, C.c_void_p(stream_ptr))
+        return n_frames
+
+    def fetch_bow(self, i: int):
+        """vocabulary.BowArrays of frame i of the last bow(); synchronises the device."""
+        import torch
+        from .vocabulary import BowArrays
+        if self._bow is None or not 0 <= int(i) < self._bow_frames:
+            raise IndexError("no such frame in the last bow()")
+        torch.cuda.synchronize()
+        b, i = self._bow, int(i)
+        nw, nn, nk, _ = b["per"][:, i].tolist()
+        ints = b["ints"][:, i, :max(nw, nn, nk)].cpu().numpy()
+        return BowArrays(ints[0, :nw].copy(), b["weight"][i, :nw].cpu().numpy(), ints[1, :nn].copy(),
+                         ints[2, :nn].copy(), ints[3, :nk].copy(), nk)
+
+    def bow_status(self) -> int:
+        """OR of the ORBFE_BOW_* flags of every bow() so far (0: no count was clamped); synchronises."""
+        import torch
+        if self._bow is None:
+            return 0
+        torch.cuda.synchronize()
+        return int(self._bow["per"][3, 0])
 
     def fetch_image(self, i: int) -> tuple[np.ndarray, np.ndarray]:
         kps = np.empty(self.kp_cap, KP_DTYPE)

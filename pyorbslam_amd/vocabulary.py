@@ -4,9 +4,11 @@ The reference descends the vocabulary tree one descriptor at a time in Python, w
 per child (FORB.distance, FORB.py:30-32): ~10 us x k x L per feature, ~1 s per 2000-feature frame on
 ORBvoc (k=10, L=6).  Here the text file is parsed natively (orbfe_vocab_load_text), the tree is laid
 out child-run-contiguous in HBM, and every descriptor of a frame (or of many frames) descends in one
-k_vocab_descend launch (pyorbslam_amd/csrc/orbfe_vocab.hip).  The host keeps only what is inherently
-sequential: threading the previous feature's node id through descents that stop above the node level,
-and accumulating the BoW weights in feature order so every float sum matches the reference's.
+k_vocab_descend launch (pyorbslam_amd/csrc/orbfe_vocab.hip).  What is sequential in the reference — threading
+the previous feature's node id through descents that stop above the node level, accumulating the BoW weights in
+feature order, the total in word order — is done per frame by k_bow_assemble on the device (one workgroup per
+frame, every float sum in the reference's order); the host only turns the arrays into the dicts.  A frame longer
+than ORBFE_BOW_MAX_FRAME is assembled on the host (_assemble).
 
 score / score_many (TemplatedVocabulary.py:99-106): "L1_NORM", the scoring System.py:38 builds the vocabulary
 with, runs on the device (k_bow_score, pyorbslam_amd/csrc/orbfe_kfdb.hip) in the canonical summation order
@@ -17,11 +19,12 @@ from __future__ import annotations
 
 import ctypes as C
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _lib
-from ._lib import ORBFE_EFORMAT, ORBFE_EREJECT, VocabInfo, call, check, lib, ptr
+from ._lib import ORBFE_BOW_MAX_FRAME, ORBFE_EFORMAT, ORBFE_EREJECT, BowOut, VocabInfo, call, check, lib, ptr
 
 
 # ScoringObject.py:30-92, restated for the host (no device path)
@@ -87,6 +90,25 @@ def l1_score_many(bv, others):
 
 def _l1_score(v1, v2):
     return l1_score_many(v1, [v2])[0]
+
+
+class BowArrays(NamedTuple):
+    """One frame's BowVector and FeatureVector as arrays (the device's CSR form)."""
+    word: np.ndarray     # int32, distinct word ids, ascending
+    weight: np.ndarray   # float64, their normalised weights
+    node: np.ndarray     # int32, distinct node ids, ascending
+    end: np.ndarray      # int32, exclusive end of each node's run in idx
+    idx: np.ndarray      # int32, kept feature indices grouped by node, ascending within a run
+    n_kept: int
+
+    def dicts(self):
+        """(BowVector, FeatureVector) as transform() returns them: OrderedDicts of Python ints and floats in
+        ascending key order, ({}, {}) for a frame without kept features."""
+        if self.n_kept == 0:
+            return {}, {}
+        idx, end = self.idx.tolist(), self.end.tolist()
+        fv = OrderedDict((nd, idx[a:b]) for nd, a, b in zip(self.node.tolist(), [0] + end[:-1], end))
+        return OrderedDict(zip(self.word.tolist(), self.weight.tolist())), fv
 
 
 class TemplatedVocabulary:
@@ -219,20 +241,52 @@ class TemplatedVocabulary:
                 bv[key] /= total
         return bv, OrderedDict(sorted(feats.items()))
 
+    def bow_many(self, frames, levels_up=4):
+        """BowArrays of every frame: the descent and k_bow_assemble (one workgroup per frame) in one
+        orbfe_vocab_bow call, no per-feature host work.  word / weight are what BowDatabase.add_arrays and
+        query_arrays take.  Raises OrbfeError (EINVAL) for a frame longer than ORBFE_BOW_MAX_FRAME."""
+        frames = [np.ascontiguousarray(f, np.uint8).reshape(-1, 32) for f in frames]
+        nf = len(frames)
+        if nf == 0:
+            return []
+        off = np.zeros(nf + 1, np.int64)
+        np.cumsum([len(f) for f in frames], out=off[1:])
+        n = int(off[-1])
+        q = np.ascontiguousarray(np.concatenate(frames))
+        ints = np.zeros((4, max(n, 1)), np.int32)   # bow_word, fv_node, fv_end, fv_idx
+        per = np.zeros((3, nf), np.int32)           # n_words, n_nodes, n_kept
+        weight = np.zeros(max(n, 1), np.float64)
+        out = BowOut(n_words=ptr(per[0]), bow_word=ptr(ints[0]), bow_weight=ptr(weight), n_nodes=ptr(per[1]),
+                     fv_node=ptr(ints[1]), fv_end=ptr(ints[2]), fv_idx=ptr(ints[3]), n_kept=ptr(per[2]), status=None)
+        call("orbfe_vocab_bow", self._handle(), ptr(q), ptr(off), nf, int(self.L - levels_up), C.byref(out))
+        res = []
+        for f, o in enumerate(off[:-1].tolist()):
+            nw, nn, nk = per[:, f].tolist()
+            res.append(BowArrays(ints[0, o:o + nw], weight[o:o + nw], ints[1, o:o + nn], ints[2, o:o + nn],
+                                 ints[3, o:o + nk], nk))
+        return res
+
+    def last_bow_ms(self) -> float:
+        """Kernel time (descent + assembly) of the last bow_many on this vocabulary."""
+        ms = C.c_float()
+        call("orbfe_vocab_bow_last_ms", self._handle(), C.byref(ms))
+        return float(ms.value)
+
     # TemplatedVocabulary.py:108-129
     def transform(self, features, levels_up=4):
-        return self._assemble(*self.descend(features, levels_up))
+        return self.transform_many([features], levels_up)[0]
 
     def transform_many(self, frames, levels_up=4):
-        """transform() of several frames with ONE kernel launch over all their descriptors."""
+        """transform() of several frames with ONE descent launch and ONE assembly launch over all of them.  A frame
+        longer than ORBFE_BOW_MAX_FRAME is descended on the device and assembled on the host (_assemble)."""
         frames = [np.ascontiguousarray(f, np.uint8).reshape(-1, 32) for f in frames]
-        if not frames:
-            return []
-        word, node, w = self.descend(np.concatenate(frames), levels_up)
-        out, o = [], 0
-        for f in frames:
-            out.append(self._assemble(word[o:o + len(f)], node[o:o + len(f)], w[o:o + len(f)]))
-            o += len(f)
+        short = [i for i, f in enumerate(frames) if len(f) <= ORBFE_BOW_MAX_FRAME]
+        out = [None] * len(frames)
+        for i, a in zip(short, self.bow_many([frames[i] for i in short], levels_up)):
+            out[i] = a.dicts()
+        for i, f in enumerate(frames):
+            if out[i] is None:
+                out[i] = self._assemble(*self.descend(f, levels_up))
         return out
 
     # TemplatedVocabulary.py:131-160
