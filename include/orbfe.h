@@ -32,10 +32,10 @@ extern "C" {
 /* ABI revision of this header (orbfe_abi_version() returns the library's).  4: ORBFE_NSTAGES = 5 (stage 3
  * describe, 4 stereo; the round-1 blur stage and orbfe_set_blur_fork are gone), orbfe_set_graphs,
  * orbfe_set_octree_kernel / orbfe_get_octree_kernel, orbfe_debug_detect_stats. */
-#define ORBFE_ABI_VERSION 8 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
+#define ORBFE_ABI_VERSION 9 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
                                * sides above 4 095 px are accepted (kKeyXYBits).  7: orbfe_kfdb_*, orbfe_bow_score.
                                * 8: orbfe_vocab_bow, orbfe_vocab_bow_device, orbfe_vocab_bow_scratch_bytes,
-                               * orbfe_vocab_bow_last_ms (additive) */
+                               * orbfe_vocab_bow_last_ms (additive).  9: orbfe_get_stereo_bucket_kernel (additive) */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -386,6 +386,14 @@ int orbfe_debug_detect_stats(orbfe_handle h, int64_t* stats);
  * 1 per-candidate) and the bins kernel's LDS need. */
 int orbfe_set_octree_kernel(orbfe_handle h, int32_t kernel);
 int orbfe_get_octree_kernel(orbfe_handle h, int32_t* kernel, int64_t* bins_lds_bytes);
+
+/* Where the stereo row buckets (Frame.py:170-179) of the reserved geometry are built.  Host-only, no device
+ * call.  *fused = 1: orbfe_frame_extract and orbfe_frontend_batch_device build them inside the describe launch
+ * (256-thread workgroups; the H + 1 row counters fit its LDS), 0: those calls launch the separate bucket kernel
+ * too.  *threads (optional): the workgroup size of that separate kernel for a batch of n_images images (1 024
+ * below 32 images, else 256), which orbfe_stereo_match (n_images = 2) and orbfe_stereo_batch_device always
+ * launch.  Results do not depend on either. */
+int orbfe_get_stereo_bucket_kernel(orbfe_handle h, int32_t n_images, int32_t* fused, int32_t* threads);
 
 /* ---- bag-of-words vocabulary (pyDBoW/TemplatedVocabulary.py) ---------------------------
  *

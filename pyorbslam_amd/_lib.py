@@ -40,7 +40,7 @@ class VocabInfo(C.Structure):
                 ("n_nodes", C.c_int64), ("n_words", C.c_int64), ("depth", C.c_int32), ("max_children", C.c_int32)]
 
 
-ORBFE_ABI_VERSION = 8
+ORBFE_ABI_VERSION = 9
 ORBFE_BOW_MAX_FRAME = 8192  # the longest frame k_bow_assemble takes (include/orbfe.h)
 # flags of BowOut.status
 ORBFE_BOW_OVER_OUT, ORBFE_BOW_OVER_MAX, ORBFE_BOW_OVER_FRAME, ORBFE_BOW_NEGATIVE = 1, 2, 4, 8
@@ -120,6 +120,7 @@ SIGNATURES = {
     "orbfe_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
     "orbfe_set_octree_kernel": [C.c_void_p, C.c_int32],
     "orbfe_get_octree_kernel": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+    "orbfe_get_stereo_bucket_kernel": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "orbfe_debug_detect_stats": [C.c_void_p, C.POINTER(C.c_int64)],
     "orbfe_vocab_load_text": [C.c_char_p, C.POINTER(C.c_void_p)],
     "orbfe_vocab_create": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -2092,6 +2092,15 @@ int orbfe_get_octree_kernel(orbfe_handle h, int32_t* kernel, int64_t* bins_lds_b
     });
 }
 
+int orbfe_get_stereo_bucket_kernel(orbfe_handle h, int32_t n_images, int32_t* fused, int32_t* threads) {
+    return guarded([&] {
+        if (!h || !fused || n_images <= 0) throw Error(ORBFE_EINVAL, "bad argument");
+        if (h->W <= 0) throw Error(ORBFE_ESTATE, "no geometry reserved yet");
+        *fused = orb_fuses_bucket(h->geo) ? 1 : 0;
+        if (threads) *threads = stereo_bucket_threads(n_images);
+    });
+}
+
 int orbfe_debug_detect_stats(orbfe_handle h, int64_t* stats) {
     return guarded([&] {
         if (!h || !stats) throw Error(ORBFE_EINVAL, "null argument");

@@ -121,6 +121,8 @@ hipError_t launch_orb(const Geo& g, const uint8_t* in, int64_t in_pitch, const u
                       const uint32_t* tab, hipStream_t s, int keypoints_per_wave = 0,
                       const StereoArgs* bucket = nullptr, int n_bucket = 0);
 bool orb_fuses_bucket(const Geo& g);
+// threads of the separate k_stereo_bucket launch (launch_stereo without buckets_built) for n_images images
+int stereo_bucket_threads(int n_images);
 // k_orb's item table (orb_tables on the host): 192 horizontal items + 256 centroid slots x 4 dwords
 constexpr int kOrbTabWords = 192 + 256 * 4;
 // buckets_built: k_orb's launch already built the row buckets (launch_orb's bucket argument)

@@ -4099,9 +4099,11 @@ hipError_t launch_orb(const Geo& g, const uint8_t* in, int64_t in_pitch, const u
     return hipGetLastError();
 }
 
+int stereo_bucket_threads(int n_images) { return n_images < kSmallBatchImages ? 1024 : 256; }
+
 hipError_t launch_stereo(const Geo& g, const StereoArgs& a, int n_pairs, hipStream_t s, bool buckets_built) {
     if (buckets_built) {
-    } else if (2 * n_pairs < kSmallBatchImages)
+    } else if (stereo_bucket_threads(2 * n_pairs) == 1024)
         hipLaunchKernelGGL(k_stereo_bucket<1024>, dim3(n_pairs), dim3(1024), (size_t)4 * (g.H + 1), s, g, a);
     else
         hipLaunchKernelGGL(k_stereo_bucket<256>, dim3(n_pairs), dim3(256), (size_t)4 * (g.H + 1), s, g, a);

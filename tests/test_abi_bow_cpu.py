@@ -1,4 +1,4 @@
-"""ABI 8 (orbfe_vocab_bow, orbfe_vocab_bow_device) on a GPU-less host: the symbols, the constants and the argument
+"""ABI 8's additions (orbfe_vocab_bow, orbfe_vocab_bow_device) on a GPU-less host: the symbols, the constants and the argument
 checks that come before any device call."""
 import ctypes as C
 import re
@@ -8,11 +8,12 @@ import numpy as np
 from conftest import ROOT
 
 
-def test_abi_version_is_8():
+def test_abi_version_is_9():
+    """9 = 8 (the entry points below) + orbfe_get_stereo_bucket_kernel, additive."""
     from pyorbslam_amd import _lib
-    assert _lib.lib().orbfe_abi_version() == 8 == _lib.ORBFE_ABI_VERSION
+    assert _lib.lib().orbfe_abi_version() == 9 == _lib.ORBFE_ABI_VERSION
     hdr = (ROOT / "include" / "orbfe.h").read_text()
-    assert int(re.search(r"#define ORBFE_ABI_VERSION (\d+)", hdr).group(1)) == 8
+    assert int(re.search(r"#define ORBFE_ABI_VERSION (\d+)", hdr).group(1)) == 9
 
 
 def test_new_symbols_resolve():

@@ -70,3 +70,23 @@ def test_driver_scripts_compile():
     root = Path(__file__).resolve().parents[1]
     for f in [root / "bench.py", root / "__graft_entry__.py", *sorted((root / "tools").glob("*.py"))]:
         compile(f.read_text(), str(f), "exec")
+
+
+def test_stereo_bucket_kernel_query_without_gpu():
+    """orbfe_get_stereo_bucket_kernel (ABI 9) is host-only: its argument checks, the ESTATE before a geometry is
+    reserved, and the 32-image rule of the separate bucket kernel."""
+    from pyorbslam_amd import _lib
+    L = _lib.lib()
+    assert "orbfe_get_stereo_bucket_kernel" in declared()
+    prm = _lib.make_params(300, 1.2, 3, 20, 7, 16)
+    h = C.c_void_p()
+    assert L.orbfe_create(C.byref(prm), C.byref(h)) == 0
+    try:
+        fused, threads = C.c_int32(-1), C.c_int32(-1)
+        assert L.orbfe_get_stereo_bucket_kernel(None, 2, C.byref(fused), C.byref(threads)) == _lib.ORBFE_EINVAL
+        assert L.orbfe_get_stereo_bucket_kernel(h, 2, None, C.byref(threads)) == _lib.ORBFE_EINVAL
+        assert L.orbfe_get_stereo_bucket_kernel(h, 0, C.byref(fused), C.byref(threads)) == _lib.ORBFE_EINVAL
+        assert L.orbfe_get_stereo_bucket_kernel(h, 2, C.byref(fused), C.byref(threads)) == _lib.ORBFE_ESTATE
+        assert (fused.value, threads.value) == (-1, -1)
+    finally:
+        L.orbfe_destroy(h)
