@@ -123,7 +123,9 @@ hipError_t launch_orb(const Geo& g, const uint8_t* in, int64_t in_pitch, const u
 bool orb_fuses_bucket(const Geo& g);
 // threads of the separate k_stereo_bucket launch (launch_stereo without buckets_built) for n_images images
 int stereo_bucket_threads(int n_images);
-// k_orb's item table (orb_tables on the host): 192 horizontal items + 256 centroid slots x 4 dwords
+// k_orb's item table (orb_tables on the host): 192 horizontal items + 256 centroid slots x 4 dwords.  The BRIEF
+// pattern is not part of it: its distinct sample points and the bits' slot pairs are constants of the kernel
+// (brief_distinct.inc)
 constexpr int kOrbTabWords = 192 + 256 * 4;
 // buckets_built: k_orb's launch already built the row buckets (launch_orb's bucket argument)
 hipError_t launch_stereo(const Geo& g, const StereoArgs& a, int n_pairs, hipStream_t s, bool buckets_built = false);

@@ -25,10 +25,24 @@
 
 namespace orbfe {
 
-// (x0, y0, x1, y1) of the 256 point pairs as floats: lane j reads bits j + 64 i as 4 x 16-byte loads
-__constant__ __attribute__((aligned(16))) float c_pattern[1024] = {
-#include "brief_pattern.inc"
+// The steered-BRIEF pattern by distinct sample point (brief_distinct.inc, generated from brief_pattern.inc):
+// 375 of its 512 ends are distinct.  c_points: (x, y) of the 384 slots as floats, slots 2 t and 2 t + 1 in one
+// 16-byte entry t; c_bit_slots: per descriptor bit, slot of (x0, y0) | slot of (x1, y1) << 16.
+constexpr int kBriefSlots = 384;
+#define BRIEF_POINT(x, y) x, y,
+#define BRIEF_BIT(s0, s1)
+__constant__ __attribute__((aligned(16))) float c_points[2 * kBriefSlots] = {
+#include "brief_distinct.inc"
 };
+#undef BRIEF_POINT
+#undef BRIEF_BIT
+#define BRIEF_POINT(x, y)
+#define BRIEF_BIT(s0, s1) (s0) | (s1) << 16,
+__constant__ uint32_t c_bit_slots[256] = {
+#include "brief_distinct.inc"
+};
+#undef BRIEF_POINT
+#undef BRIEF_BIT
 
 // ------------------------------------------------------------------------------- small helpers
 typedef float df2 __attribute__((ext_vector_type(2)));  // packed f32 (v_pk_mul/fma/add_f32)
@@ -2905,9 +2919,12 @@ __device__ __forceinline__ int reflect101c(int p, int n) {  // reflect-101, clam
 //    of (signed byte weights u, v, dword), 2 signed v_dot4 each on the bytes I - 128;
 //  * horizontal taps: the 189 (row pair, 4-column group) items the disc needs (a per-lane table), 10 v_dot4
 //    with shifted byte weights per row, stored row-pair interleaved as u16 pairs (dword = (H[2m][c], H[2m+1][c]));
-//  * BRIEF: lane j evaluates bits j + 64 i (i = 0..3); each of its 8 samples takes its vertical taps from
-//    4 interleaved dwords (2 ds_read2) with 4 v_dot2 whose weights depend on the sample row's parity; one
-//    ballot per 64 bits.
+//  * BRIEF: a sample's blurred value depends on its pattern point and the angle only, and 375 of the
+//    pattern's 512 ends are distinct, so every distinct point is evaluated once: lane j evaluates slots
+//    2 (j + 64 i), + 1 (i = 0..2; 384 slots, the last 9 are the window centre and unused), each from its
+//    vertical taps in 4 interleaved dwords (2 ds_read2) with 4 v_dot2 whose weights depend on the sample
+//    row's parity, and leaves the blurred bytes in a per-wave LDS buffer; lane j then reads the two ends
+//    of its bits j + 64 i (i = 0..3) back from per-lane constant addresses; one ballot per 64 bits.
 constexpr int kSrcRows = 43, kSrcDw = 12;
 constexpr int kHPairs = 22, kHGrp = 10, kHDw = 4 * kHGrp;  // H: 22 row pairs x 40 columns (dwords)
 constexpr int kOrbHItems = 3;          // horizontal items per lane (189 of 192 used)
@@ -2941,7 +2958,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
                                                     const int* __restrict__ lvl_count, orbfe_keypoint* __restrict__ out_kp,
                                                     uint8_t* __restrict__ out_desc, int* __restrict__ out_count,
                                                     const uint32_t* __restrict__ tab, int gx, StereoArgs sa, int n_bucket) {
-    __shared__ float4 s_pat[256];
+    static_assert(64 * WAVES >= kBriefSlots / 2, "one thread per s_pts entry");
+    __shared__ float4 s_pts[kBriefSlots / 2];              // (x, y) of slots 2 t, 2 t + 1
+    __shared__ uint16_t s_val[WAVES][kBriefSlots / 2];     // blurred bytes of slots 2 t | 2 t + 1 << 8
     __shared__ uint2 s_cw[64 * kOrbCSlots];                // centroid slot: signed byte weights (u, v)
     __shared__ uint32_t s_src[WAVES][kSrcRows * kSrcDw];  // staged unblurred window
     __shared__ uint32_t s_h[WAVES][kHPairs * kHDw];       // horizontal taps, row-pair interleaved u16
@@ -2966,7 +2985,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     const int wv = __builtin_amdgcn_readfirstlane(blk * WAVES + wid);
     // the lane's centroid slots: window dword (two 16-bit halves per register), the same for
     // every keypoint
-    const float4 pat_r = threadIdx.x < 256 ? ((const float4*)c_pattern)[threadIdx.x] : float4{};
+    const float4 pat_r = threadIdx.x < kBriefSlots / 2 ? ((const float4*)c_points)[threadIdx.x] : float4{};
     uint32_t cslot[kOrbCSlots / 2];
 #pragma unroll
     for (int k = 0; k < kOrbCSlots / 2; ++k) {
@@ -2983,6 +3002,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     uint32_t hit[kOrbHItems];  // per item: LDS byte address of its source dwords | of its H slot << 16
 #pragma unroll
     for (int k = 0; k < kOrbHItems; ++k) hit[k] = tab[lane + 64 * k];
+    // per bit lane + 64 i: LDS byte addresses of its two ends' blurred bytes (a register each: packed as
+    // halves they cost 8 more VALU per keypoint)
+    uint32_t bend0[4], bend1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bend0[i] = c_bit_slots[lane + 64 * i];
     // wave -> (level, first keypoint) from the level capacities (host constants)
     int l = 0, w0 = 0;
     {
@@ -3021,7 +3045,16 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     uint32_t* hb = s_h[wid];
     {
         typedef __attribute__((address_space(3))) uint32_t lds_w32;
+        typedef __attribute__((address_space(3))) uint16_t lds_w16;
         const uint32_t src_a = (uint32_t)(uintptr_t)(lds_w32*)src, hb_a = (uint32_t)(uintptr_t)(lds_w32*)hb;
+        const uint32_t val_a = (uint32_t)(uintptr_t)(lds_w16*)s_val[wid];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {  // slot s's byte is byte s of the wave's buffer
+            bend1[i] = val_a + (bend0[i] >> 16);
+            bend0[i] = val_a + (bend0[i] & 0xFFFFu);
+            // opaque, or the compiler keeps the packed table words and re-adds (8 SDWA adds per keypoint)
+            asm volatile("" : "+v"(bend0[i]), "+v"(bend1[i]));
+        }
 #pragma unroll
         for (int k = 0; k < kOrbHItems; ++k)
             hit[k] = (src_a + 4u * (hit[k] & 0xFFFFu)) | ((hb_a + 16u * (hit[k] >> 16)) << 16);
@@ -3029,7 +3062,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
         for (int k = 0; k < kOrbCSlots / 2; ++k)
             cslot[k] = (src_a + 4u * (cslot[k] & 0xFFFFu)) | ((src_a + 4u * (cslot[k] >> 16)) << 16);
     }
-    if (threadIdx.x < 256) s_pat[threadIdx.x] = pat_r;
+    if (threadIdx.x < kBriefSlots / 2) s_pts[threadIdx.x] = pat_r;
 #pragma unroll
     for (int k = 0; k < (64 * kOrbCSlots + 64 * WAVES - 1) / (64 * WAVES); ++k) {
         const int i = threadIdx.x + 64 * WAVES * k;
@@ -3178,10 +3211,20 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     typedef __attribute__((address_space(3))) const uint32_t lds_u32;
     const uint32_t kc = (uint32_t)(uintptr_t)(lds_u32*)hb + (uint32_t)(4 * (9 * kHDw + 21)) -
                         (uint32_t)(4 * kHDw) * 0xA00000u - (__float_as_uint(12582912.0f) << 2);
+    //      Every distinct sample point once (c_points): phase 1 leaves the blurred bytes of the wave's 384
+    //      slots in val (s < 2^24, so the byte is byte 2 of s: one v_perm packs an iteration's two into one
+    //      16-bit store); after one wave_sync_lds, phase 2 compares the two ends of the lane's four bits from
+    //      them.  val is written after the previous BRIEF's phase 2 read it: BRIEF(B)'s stores come after the
+    //      wave_sync_lds in front of H(B) (BRIEF(A)'s val reads were waited before its ballots), and the next
+    //      pair's BRIEF(A) after the wave_sync_lds of its stage().  The pad slots (0, 0) read H at the window
+    //      centre, which the disc's items cover, and no bit reads their bytes.
+    typedef __attribute__((address_space(3))) uint16_t lds_v16;
+    typedef __attribute__((address_space(3))) const uint8_t lds_v8;
+    lds_v16* const val = (lds_v16*)s_val[wid] + lane;
     auto brief = [&](float a, float b, int jj) {
 #pragma unroll 1
-        for (int i = 0; i < 4; ++i) {
-            const float4 pt = s_pat[lane + 64 * i];
+        for (int i = 0; i < kBriefSlots / 128; ++i) {
+            const float4 pt = s_pts[lane + 64 * i];
             uint32_t v2[2];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
@@ -3200,9 +3243,20 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
                 s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_alignbit(p2, p1, sh)), w2(48, 56), s, false);
                 s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_alignbit(p3, p2, sh)), w2(48, 34), s, false);
                 s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, p3 >> (sh & 31u)), w2(18, 0), s, false);
-                v2[e] = s >> 16;
+                v2[e] = s;
             }
-            const uint64_t bb = __ballot(v2[0] < v2[1]);  // one SDWA compare of the high halves
+            val[64 * i] = (uint16_t)__builtin_amdgcn_perm(v2[1], v2[0], 0x0c0c0602u);  // s0 >> 16 | (s1 >> 16) << 8
+        }
+        wave_sync_lds();  // val complete
+        uint32_t e0[4], e1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            e0[i] = *(lds_v8*)(uintptr_t)bend0[i];
+            e1[i] = *(lds_v8*)(uintptr_t)bend1[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t bb = __ballot(e0[i] < e1[i]);
             // lane 4 jj + i keeps this ballot: two v_writelane (a select chain or a store per iteration measured
             // 3-5 % slower in round 2)
             mine_lo = writelane_m0(mine_lo, (uint32_t)bb, 4 * jj + i);
@@ -3257,7 +3311,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
         brief(aA, bA, j);
         record(j, ax, ay, angA, keyA);
         if (has_b) {
-            wave_sync_lds();  // BRIEF A's hb reads are complete (waited before its ballots)
+            // BRIEF A's hb reads are complete (waited before the val stores they fed) and so are its val
+            // reads (waited before its ballots): H(B) may overwrite hb, BRIEF B val
+            wave_sync_lds();
             hpass();
             wave_sync_lds();  // hb complete
             brief(aB, bB, j + 1);
