@@ -35,7 +35,9 @@ extern "C" {
 #define ORBFE_ABI_VERSION 9 /* 6: compact gather records pack x | y << 14 | octave << 28 (was 12 / 12 / 24); level
                                * sides above 4 095 px are accepted (kKeyXYBits).  7: orbfe_kfdb_*, orbfe_bow_score.
                                * 8: orbfe_vocab_bow, orbfe_vocab_bow_device, orbfe_vocab_bow_scratch_bytes,
-                               * orbfe_vocab_bow_last_ms (additive).  9: orbfe_get_stereo_bucket_kernel (additive) */
+                               * orbfe_vocab_bow_last_ms (additive).  9: orbfe_get_stereo_bucket_kernel (additive).
+                               * Still 9: orbfe_bow_match, orbfe_bow_match_device, orbfe_bow_match_last_ms and
+                               * orbfe_bow_match_out only add entry points and a struct; find them by symbol */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -496,6 +498,68 @@ int orbfe_vocab_bow(orbfe_vocab_handle v, const uint8_t* desc32, const int64_t* 
                     int32_t nid_level, const orbfe_bow_out* out);
 /* Kernel time of the last orbfe_vocab_bow (descent + assembly, ms, HIP events), for measurement. */
 int orbfe_vocab_bow_last_ms(orbfe_vocab_handle v, float* ms);
+
+/* ---- BoW-guided matching of many frame pairs (ORBMatcher.search_by_BoW_kf_f / _kf_kf, ORBMatcher.py:21-213) ----
+ *
+ * k_bow_match, one launch for n_pairs pairs (frame 1, frame 2) of one set of frames.  A frame is n descriptors, n
+ * float angles, optionally one eligibility byte per feature and side (non-zero = eligible, a NULL array = all),
+ * and a feature vector in orbfe_bow_out's CSR layout: nodes strictly ascending, every feature index in at most one
+ * run.  A frame may be in many pairs, on either side, and paired with itself.  Per pair and per node both frames
+ * hold, frame 1's run is walked in order; an eligible i1 looks at the i2 of frame 2's run, in run order, that are
+ * eligible and not yet matched in this pair: best1 = the smallest Hamming distance, best_i2 the first i2 attaining
+ * it, best2 = the second smallest distance of the multiset (256 / -1 / 256 without candidates).  i1 is matched to
+ * best_i2 iff best1 < th (<= th when inclusive != 0) and (double)best1 < nnratio * (double)best2 (one IEEE double
+ * product).  Then best_i2 is blocked for the later i1 of the pair, and the rotation bin is
+ * rint(rot * (1.0 / 30)) with rot = (double)angle1[i1] - (double)angle2[best_i2], + 360.0 when negative, bin 30
+ * taken as 0 (angles outside [0, 360] can give other values: those are recorded as bin 31).
+ * search_by_BoW_kf_kf is th = 50 exclusive with both sides' eligibility, _kf_f th = 50 inclusive with side 1's.
+ * Keeping the three fullest bins (ORBMatcher.compute_three_maxima) is left to the caller: the reference ranks
+ * equal counts with NumPy's unstable argsort.
+ * The longest frame taken is ORBFE_BOW_MAX_FRAME features (the blocked flags stay in LDS).
+ * Outputs per pair p, each written in full by the kernel (no pre-fill needed; entries past n untouched):
+ *   match12[p * out_stride + i1] = i2 or -1 (i1 < n1)      match21[p * out_stride + i2] = i1 or -1 (i2 < n2)
+ *   bin12[p * out_stride + i1]   = rotation bin or -1       hist[p * 32 + b] = matches in bin b
+ *   n_raw[p] = matches of the pair */
+typedef struct orbfe_bow_match_out {
+    int32_t* match12;
+    int32_t* match21;
+    int8_t* bin12;
+    int32_t* hist;
+    int32_t* n_raw;
+    int32_t* status; /* ONE word: the OR of the ORBFE_BOW_* flags over all pairs (the device entry's caller zeroes
+                      * it; the host entry zeroes it itself and accepts NULL) */
+} orbfe_bow_match_out;
+#define ORBFE_BOW_BAD_PAIR 16 /* a pair named a frame outside [0, n_frames): left all-unmatched */
+/* Device pointers, enqueued on hip_stream without synchronising and without allocating.  Frames are addressed as in
+ * orbfe_vocab_bow_device: frame f is d_count[f * count_stride] descriptors from descriptor f * frame_stride of
+ * d_desc32 (16-byte aligned), its feature vector n_nodes[f] entries from entry f * fv_stride of d_fv's fv_node /
+ * fv_end / fv_idx (what orbfe_vocab_bow_device wrote with out_stride = fv_stride).  The angle of feature i of frame
+ * f is d_angle[(f * frame_stride + i) * angle_stride]: angle_stride = 6 on &kps->angle of an orbfe_batch_view, 1
+ * on a plain array.  Side s's eligibility of feature i of frame f is d_elig<s>[f * elig<s>_stride + i] (any
+ * non-zero byte; an int8 stereo status array qualifies), NULL = all eligible.  d_pairs: n_pairs x 2 frame indices.
+ * Counts are read on the device, clamped to out_stride, ORBFE_BOW_MAX_FRAME and frame_stride and flagged like
+ * orbfe_vocab_bow_device's; node counts, run ends and feature indices outside a frame's clamped range are ignored,
+ * so nothing is read or written past it.  A pair naming a frame outside [0, n_frames) sets ORBFE_BOW_BAD_PAIR and
+ * stays unmatched.  n_pairs = 0 launches nothing. */
+int orbfe_bow_match_device(const uint8_t* d_desc32, int64_t frame_stride, const int32_t* d_count, int64_t count_stride,
+                           int32_t n_frames, const float* d_angle, int64_t angle_stride, const uint8_t* d_elig1,
+                           int64_t elig1_stride, const uint8_t* d_elig2, int64_t elig2_stride,
+                           const orbfe_bow_out* d_fv, int64_t fv_stride, const int32_t* d_pairs, int32_t n_pairs,
+                           int32_t th, int32_t inclusive, double nnratio, const orbfe_bow_match_out* d_out,
+                           int64_t out_stride, void* hip_stream);
+/* The same over host buffers, synchronous.  Frame f is features [off[f], off[f + 1]) of desc32 / angle / elig1 /
+ * elig2 (off[0] = 0); its nodes are entries [fv_off[f], fv_off[f + 1]) of fv_node / fv_end (fv_off[0] = 0, run ends
+ * relative to the frame), its feature indices start at fv_idx[off[f]].  Outputs as above with out_stride >= the
+ * longest frame of the pairs.  Everything is validated before any device call: ORBFE_EINVAL when nodes are not
+ * strictly ascending, run ends decrease or pass the frame's length, a feature index is out of range or appears
+ * twice in a frame, a pair names a frame that does not exist, a frame is longer than ORBFE_BOW_MAX_FRAME, or a
+ * needed pointer is NULL.  Process-wide buffers, stream and events: concurrent callers take turns. */
+int orbfe_bow_match(const uint8_t* desc32, const float* angle, const uint8_t* elig1, const uint8_t* elig2,
+                    const int64_t* off, int32_t n_frames, const int64_t* fv_off, const int32_t* fv_node,
+                    const int32_t* fv_end, const int32_t* fv_idx, const int32_t* pairs, int32_t n_pairs, int32_t th,
+                    int32_t inclusive, double nnratio, const orbfe_bow_match_out* out, int64_t out_stride);
+/* Kernel time of the last orbfe_bow_match (ms, HIP events), for measurement. */
+int orbfe_bow_match_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

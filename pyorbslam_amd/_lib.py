@@ -52,6 +52,14 @@ class BowOut(C.Structure):
                                           "fv_idx", "n_kept", "status")]
 
 
+ORBFE_BOW_BAD_PAIR = 16  # orbfe_bow_match_device: a pair named a frame that does not exist
+
+
+class BowMatchOut(C.Structure):
+    """orbfe_bow_match_out: caller-owned output arrays of orbfe_bow_match / orbfe_bow_match_device."""
+    _fields_ = [(k, C.c_void_p) for k in ("match12", "match21", "bin12", "hist", "n_raw", "status")]
+
+
 # cv::KeyPoint tuple layout (opencv_type_casters.h:106-108)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4")])
@@ -148,6 +156,14 @@ SIGNATURES = {
     "orbfe_bow_score": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "orbfe_kfdb_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
+    "orbfe_bow_match_device": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BowOut), C.c_int64, C.c_void_p,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(BowMatchOut), C.c_int64,
+                               C.c_void_p],
+    "orbfe_bow_match": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                        C.POINTER(BowMatchOut), C.c_int64],
+    "orbfe_bow_match_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BatchView, BowOut, call, ptr
+from ._lib import KP_DTYPE, BatchView, BowMatchOut, BowOut, call, ptr
 
 KITTI_BF = 386.1448  # KITTI00-02.yaml Camera.bf
 KITTI_FX = 718.856   # KITTI00-02.yaml Camera.fx
@@ -47,6 +47,7 @@ class StereoFrontEnd:
         call("orbfe_batch_view_get", h, C.byref(v))
         self.kp_cap = v.kp_cap
         self._bow, self._bow_frames = None, 0  # bow()'s device buffers, made on its first call
+        self._bow_step, self._match = 1, None  # match_bow()'s outputs, made on its first call
         self.scales = np.zeros(int(nlevels), np.float32)  # the level scale factors (compact records)
         call("orbfe_get_scales", h, self.scales.ctypes.data_as(C.c_void_p), None, None, None, None)
 
@@ -121,7 +122,7 @@ class StereoFrontEnd:
             torch.cuda.synchronize()  # once: the fills above ran on torch's stream, the kernels run on stream_ptr
             self._bow = dict(ints=ints, per=per, weight=weight, scratch=scratch, out=out)
         b = self._bow
-        self._bow_frames = n_frames
+        self._bow_frames, self._bow_step = n_frames, step
         if n_frames:
             call("orbfe_vocab_bow_device", vocab._handle(), C.c_void_p(v.desc), step * cap, C.c_void_p(v.count), step,
                  n_frames, int(vocab.L - levels_up), cap, C.byref(b["out"]), C.c_void_p(b["scratch"].data_ptr()),
@@ -141,8 +142,88 @@ class StereoFrontEnd:
         return BowArrays(ints[0, :nw].copy(), b["weight"][i, :nw].cpu().numpy(), ints[1, :nn].copy(),
                          ints[2, :nn].copy(), ints[3, :nk].copy(), nk)
 
+    def match_bow(self, pairs, th: int = 50, inclusive: bool = False, nnratio: float = 1.0, eligible=None,
+                  stream_ptr: int = 0) -> int:
+        """Enqueue the BoW-guided match (k_bow_match, ORBMatcher.py:21-213 before the rotation rejection) of frame
+        pairs of the last bow() on stream_ptr (the stream bow() ran on): orbfe_bow_match_device on the batch view's
+        desc / kps and bow()'s resident feature vectors.  pairs: (P, 2) frame indices of that bow() (with
+        side="left" frame p is pair p's left image).  eligible: None (every feature), "stereo" (side="left" only:
+        the features with a stereo match, the pair's status array, on both sides) or an (n_frames, kp_cap) mask
+        used for both sides.  Returns P; fetch_bow_matches(p) reads one pair.  The outputs are allocated on the
+        first call and kept (and grown when a later call brings more pairs)."""
+        import torch
+        if self._bow is None or not self._bow_frames:
+            raise RuntimeError("match_bow needs the feature vectors of a bow() call first")
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n_pairs, cap, step = len(pairs), self.kp_cap, self._bow_step
+        v = BatchView()
+        call("orbfe_batch_view_get", self._h, C.byref(v))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        own_stream = stream_ptr != torch.cuda.current_stream().cuda_stream
+        elig_ptr, elig_stride, mask = None, 0, None
+        if isinstance(eligible, str):
+            if eligible != "stereo" or step != 2:
+                raise ValueError('eligible="stereo" needs bow(side="left")')
+            elig_ptr, elig_stride = C.c_void_p(v.status), cap
+        elif eligible is not None:
+            m = np.ascontiguousarray(eligible).astype(np.uint8, copy=False)
+            if m.shape != (self._bow_frames, cap):
+                raise ValueError("eligible must be (n_frames, kp_cap)")
+            mask = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+            elig_ptr, elig_stride = C.c_void_p(mask.data_ptr()), cap
+        mt = self._match
+        if mt is None or mt["cap_pairs"] < n_pairs:
+            cp = max(n_pairs, 2 * self.max_pairs)
+            mt = dict(cap_pairs=cp, ints=torch.zeros((2, cp, cap), dtype=torch.int32, device=dev),
+                      bins=torch.zeros((cp, cap), dtype=torch.int8, device=dev),
+                      hist=torch.zeros((cp, 32), dtype=torch.int32, device=dev),
+                      n_raw=torch.zeros(cp, dtype=torch.int32, device=dev),
+                      pairs=torch.zeros((cp, 2), dtype=torch.int32, device=dev))
+            mt["out"] = BowMatchOut(match12=mt["ints"][0].data_ptr(), match21=mt["ints"][1].data_ptr(),
+                                    bin12=mt["bins"].data_ptr(), hist=mt["hist"].data_ptr(),
+                                    n_raw=mt["n_raw"].data_ptr(), status=self._bow["per"][3].data_ptr())
+            self._match = mt
+            own_stream = True
+        mt["host_pairs"], mt["n_pairs"], mt["mask"] = pairs.copy(), n_pairs, mask
+        if n_pairs:
+            mt["pairs"][:n_pairs].copy_(torch.from_numpy(pairs))
+            if own_stream:  # the fills and the upload ran on torch's stream, the kernel runs on stream_ptr
+                torch.cuda.current_stream().synchronize()
+            call("orbfe_bow_match_device", C.c_void_p(v.desc), step * cap, C.c_void_p(v.count), step, self._bow_frames,
+                 C.c_void_p(v.kps + KP_DTYPE.fields["angle"][1]), KP_DTYPE.itemsize // 4, elig_ptr, elig_stride,
+                 elig_ptr, elig_stride, C.byref(self._bow["out"]), cap, C.c_void_p(mt["pairs"].data_ptr()), n_pairs,
+                 int(th), int(bool(inclusive)), float(nnratio), C.byref(mt["out"]), cap, C.c_void_p(stream_ptr))
+        return n_pairs
+
+    def fetch_bow_matches(self, p: int, check_orientation: bool = True):
+        """(match12, match21, n) of pair p of the last match_bow(): match12[i1] = i2 or -1 over frame 1's features,
+        match21 the inverse over frame 2's, n the matches left after the reference's rotation rejection (the
+        three fullest bins by ORBMatcher.compute_three_maxima, on the host; check_orientation=False keeps every
+        match).  Synchronises the device."""
+        import torch
+        from .matcher import ORBMatcher
+        mt = self._match
+        if mt is None or not 0 <= int(p) < mt["n_pairs"]:
+            raise IndexError("no such pair in the last match_bow()")
+        torch.cuda.synchronize()
+        p = int(p)
+        n = C.c_int32()
+        lens = []
+        for f in mt["host_pairs"][p].tolist():
+            k = 0
+            if 0 <= f < self._bow_frames:
+                call("orbfe_batch_fetch", self._h, f * self._bow_step, None, None, self.kp_cap, C.byref(n))
+                k = min(n.value, self.kp_cap)
+            lens.append(k)
+        m12 = mt["ints"][0, p, :lens[0]].cpu().numpy()
+        m21 = mt["ints"][1, p, :lens[1]].cpu().numpy()
+        b12 = mt["bins"][p, :lens[0]].cpu().numpy()
+        return ORBMatcher(1.0, bool(check_orientation))._bow_reject(m12, m21, b12, mt["hist"][p].cpu().numpy(),
+                                                                    int(mt["n_raw"][p]))
+
     def bow_status(self) -> int:
-        """OR of the ORBFE_BOW_* flags of every bow() so far (0: no count was clamped); synchronises."""
+        """OR of the ORBFE_BOW_* flags of every bow() and match_bow() so far (0: no count was clamped, no pair named
+        a missing frame); synchronises."""
         import torch
         if self._bow is None:
             return 0

@@ -382,6 +382,95 @@ def _descriptor_rows(descs: list) -> np.ndarray:
     return np.stack([np.asarray(d, np.uint8).reshape(32) for d in descs])
 
 
+def bow_match_arrays(desc, angle, off, fv_off, fv_node, fv_end, fv_idx, pairs, th=TH_LOW, inclusive=False,
+                     nnratio=1.0, elig1=None, elig2=None) -> dict:
+    """orbfe_bow_match (k_bow_match, include/orbfe.h): the BoW-guided match of ORBMatcher.py:21-213 for many frame
+    pairs in one launch, before the rotation rejection.  Frame f is features [off[f], off[f + 1]) of desc (x 32
+    u8) / angle (f32) / elig1 / elig2 (u8, None = all eligible), its feature vector nodes [fv_off[f], fv_off[f + 1])
+    of fv_node / fv_end with the indices at fv_idx[off[f]:]; pairs: (P, 2) frame indices.  Returns match12,
+    match21 (P, stride) int32, bin12 (P, stride) int8, hist (P, 32), n_raw (P,) and status; row p holds n1 / n2
+    entries, the rest stays -1."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    desc, angle = arr(desc, np.uint8), arr(angle, np.float32)
+    off, fv_off = arr(off, np.int64), arr(fv_off, np.int64)
+    fv_node, fv_end, fv_idx = arr(fv_node, np.int32), arr(fv_end, np.int32), arr(fv_idx, np.int32)
+    elig1, elig2 = arr(elig1, np.uint8), arr(elig2, np.uint8)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    n_frames, n_pairs = max(len(off) - 1, 0), len(pairs)
+    n = int(off[-1]) if n_frames > 0 else 0
+    for a, per in ((desc, 32), (angle, 1), (elig1, 1), (elig2, 1), (fv_idx, 1)):
+        if a is not None and a.size < n * per:
+            raise ValueError("a per-feature array is shorter than off[-1] features")
+    if n_frames > 0 and (len(fv_off) != n_frames + 1 or min(len(fv_node), len(fv_end)) < int(fv_off[-1])):
+        raise ValueError("fv_off / fv_node / fv_end do not cover the frames")
+    stride = int(np.diff(off).max()) if n_frames > 0 else 0
+    m12 = np.full((n_pairs, stride), -1, np.int32)
+    m21 = np.full((n_pairs, stride), -1, np.int32)
+    b12 = np.full((n_pairs, stride), -1, np.int8)
+    hist = np.zeros((n_pairs, 32), np.int32)
+    n_raw = np.zeros(n_pairs, np.int32)
+    status = np.zeros(1, np.int32)
+    out = _lib.BowMatchOut(match12=m12.ctypes.data, match21=m21.ctypes.data, bin12=b12.ctypes.data,
+                           hist=hist.ctypes.data, n_raw=n_raw.ctypes.data, status=status.ctypes.data)
+    call("orbfe_bow_match", ptr(desc), ptr(angle), ptr(elig1), ptr(elig2), ptr(off), n_frames, ptr(fv_off),
+         ptr(fv_node), ptr(fv_end), ptr(fv_idx), ptr(pairs), n_pairs, int(th), int(bool(inclusive)), float(nnratio),
+         C.byref(out), stride)
+    return dict(match12=m12, match21=m21, bin12=b12, hist=hist, n_raw=n_raw, status=int(status[0]))
+
+
+class _BowFrame:
+    __slots__ = ("desc", "angle", "elig", "fv_node", "fv_end", "fv_idx")
+
+
+def _bow_frame(obj, kps, vp):
+    """Array form of a keyframe / frame for k_bow_match: descriptors, the angles of `kps` as float32, eligibility
+    from the map-point list `vp` (None: every feature) and the feature vector as CSR.  None when the arrays cannot
+    express the object (the caller then takes the single search): an angle that is not a double holding a float32
+    value, feature-vector keys not ascending, an index outside the frame or in two runs, descriptors that are
+    not n x 32 u8, a map-point list of another length, or a frame above the kernel's cap."""
+    desc = np.asarray(obj.mDescriptors)
+    if desc.ndim != 2 or desc.shape[1] != 32 or desc.dtype != _U8_DT:
+        return None
+    n = len(desc)
+    if n > _lib.ORBFE_BOW_MAX_FRAME or len(kps) != n or (vp is not None and len(vp) != n):
+        return None
+    if kps is obj.mvKeysUn:
+        ang = _angles(obj)
+    else:
+        vals = list(map(_ANGLE, kps))
+        ang = np.array(vals, np.float64) if set(map(type, vals)) <= _F64_SET else None
+    if ang is None:
+        return None
+    a32 = ang.astype(np.float32)
+    if not np.array_equal(a32.astype(np.float64), ang):
+        return None
+    fv = obj.mFeatVec
+    nodes = list(fv)
+    if not set(map(type, nodes)) <= _INT_SET or any(b <= a for a, b in zip(nodes, nodes[1:])):
+        return None
+    if nodes and not -2**31 <= nodes[0] <= nodes[-1] < 2**31:
+        return None
+    runs = [fv[k] for k in nodes]
+    lens = np.fromiter(map(len, runs), np.int64, count=len(runs))
+    try:
+        idx = np.fromiter((i for r in runs for i in r), np.int64, count=int(lens.sum()))
+    except (TypeError, ValueError):
+        return None
+    if len(idx) and (idx.min() < 0 or idx.max() >= n or len(np.unique(idx)) != len(idx)):
+        return None
+    f = _BowFrame()
+    f.desc, f.angle = desc, a32
+    if vp is None:
+        f.elig = np.ones(n, np.uint8)
+    else:
+        f.elig = np.fromiter((1 if p and not p.is_bad() else 0 for p in vp), np.uint8, count=n)
+    f.fv_node = np.array(nodes, np.int32)
+    f.fv_end = np.cumsum(lens).astype(np.int32)
+    f.fv_idx = idx.astype(np.int32)
+    return f
+
+
 class ORBMatcher:
     def __init__(self, nnratio=1, checkOri=True):
         self.mfNNratio = nnratio
@@ -899,6 +988,92 @@ class ORBMatcher:
         if self.mbCheckOrientation:
             n_matches -= self._reject_by_rotation(rot_hist, lambda i: vpMatches12.__setitem__(i, None))
         return n_matches, vpMatches12
+
+    # ------------------------------------------------------------------------------------------------
+    # the two BoW searches for many candidates at once: one k_bow_match launch (orbfe_bow_match)
+
+    def _bow_many(self, frames, pairs, inclusive, elig2):
+        """One launch over array forms of `frames` (None where a frame has none); pairs (a, b) index frames.
+        Returns per pair None (an operand the arrays cannot express: the caller takes the single search) or
+        (match12, match21, n) after the rotation rejection."""
+        ratio = self.mfNNratio
+        ok = type(ratio) in _DOUBLE_OR_INT_SET
+        live = [p for p, (a, b) in enumerate(pairs) if ok and frames[a] is not None and frames[b] is not None]
+        out = [None] * len(pairs)
+        if not live:
+            return out
+        used = sorted({f for p in live for f in pairs[p]})
+        slot = {f: k for k, f in enumerate(used)}
+        fa = [frames[f] for f in used]
+        off = np.zeros(len(fa) + 1, np.int64)
+        np.cumsum([len(f.desc) for f in fa], out=off[1:])
+        fv_off = np.zeros(len(fa) + 1, np.int64)
+        np.cumsum([len(f.fv_node) for f in fa], out=fv_off[1:])
+        cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs), dt) if xs else np.zeros(0, dt)  # noqa: E731
+        fv_idx = np.zeros(int(off[-1]), np.int32)
+        for k, f in enumerate(fa):
+            fv_idx[off[k]:off[k] + len(f.fv_idx)] = f.fv_idx
+        elig = cat([f.elig for f in fa], np.uint8)
+        r = bow_match_arrays(cat([f.desc for f in fa], np.uint8).reshape(-1, 32), cat([f.angle for f in fa], np.float32),
+                             off, fv_off, cat([f.fv_node for f in fa], np.int32), cat([f.fv_end for f in fa], np.int32),
+                             fv_idx, np.array([[slot[a], slot[b]] for a, b in (pairs[p] for p in live)], np.int32),
+                             TH_LOW, inclusive, float(ratio), elig, elig if elig2 else None)
+        for k, p in enumerate(live):
+            n1, n2 = len(frames[pairs[p][0]].desc), len(frames[pairs[p][1]].desc)
+            if r["hist"][k, HISTO_LENGTH:].any():  # an angle outside [0, 360]: the reference's own indexing decides
+                continue
+            out[p] = self._bow_reject(r["match12"][k, :n1], r["match21"][k, :n2], r["bin12"][k, :n1], r["hist"][k],
+                                      int(r["n_raw"][k]))
+        return out
+
+    def _bow_reject(self, match12, match21, bin12, hist, n_raw):
+        """The rotation rejection of the BoW searches over k_bow_match's raw outputs (ORBMatcher.py:108-116,
+        202-210): compute_three_maxima on the histogram, as the reference ranks it on this host."""
+        if not self.mbCheckOrientation:
+            return match12, match21, n_raw
+        keep = np.zeros(HISTO_LENGTH + 2, bool)
+        keep[np.asarray(self.compute_three_maxima([range(c) for c in hist[:HISTO_LENGTH].tolist()], HISTO_LENGTH))] = True
+        drop = (match12 >= 0) & ~keep[bin12]
+        match12, match21 = match12.copy(), match21.copy()
+        match21[match12[drop]] = -1
+        match12[drop] = -1
+        return match12, match21, n_raw - int(drop.sum())
+
+    def search_by_BoW_kf_kf_many(self, pKF1, kfs2):
+        """[search_by_BoW_kf_kf(pKF1, kf) for kf in kfs2] (LoopClosing.compute_sim3's loop, LoopClosing.py:156-166),
+        value for value, with one launch for the whole list."""
+        kfs2 = list(kfs2)
+        vps = [pKF1.get_map_point_matches()] + [kf.get_map_point_matches() for kf in kfs2]
+        frames = [_bow_frame(kf, kf.mvKeysUn, vp) for kf, vp in zip([pKF1] + kfs2, vps)]
+        res = self._bow_many(frames, [(0, j + 1) for j in range(len(kfs2))], False, True)
+        out = []
+        for j, (kf, r) in enumerate(zip(kfs2, res)):
+            if r is None:
+                out.append(self.search_by_BoW_kf_kf(pKF1, kf))
+                continue
+            m12 = r[0].tolist()
+            vp2 = vps[j + 1]
+            out.append((r[2], [vp2[i2] if i2 >= 0 else None for i2 in m12]))
+        return out
+
+    def search_by_BoW_kf_f_many(self, kfs, frame):
+        """[search_by_BoW_kf_f(kf, frame) for kf in kfs] (Tracking.relocalization's loop, Tracking.py:677-685),
+        value for value, with one launch for the whole list."""
+        kfs = list(kfs)
+        vps = [kf.get_map_point_matches() for kf in kfs]
+        frames = [_bow_frame(kf, kf.mvKeysUn, vp) for kf, vp in zip(kfs, vps)]
+        fr = _bow_frame(frame, frame.mvKeys, None)
+        if fr is not None and len(fr.desc) != frame.N:
+            fr = None
+        frames.append(fr)
+        res = self._bow_many(frames, [(j, len(kfs)) for j in range(len(kfs))], True, False)
+        out = []
+        for kf, vp, r in zip(kfs, vps, res):
+            if r is None:
+                out.append(self.search_by_BoW_kf_f(kf, frame))
+                continue
+            out.append((r[2], [vp[i1] if i1 >= 0 else None for i1 in r[1].tolist()]))
+        return out
 
     @staticmethod
     def _sim3_to_pose(Scw):
