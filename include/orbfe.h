@@ -37,7 +37,8 @@ extern "C" {
                                * 8: orbfe_vocab_bow, orbfe_vocab_bow_device, orbfe_vocab_bow_scratch_bytes,
                                * orbfe_vocab_bow_last_ms (additive).  9: orbfe_get_stereo_bucket_kernel (additive).
                                * Still 9: orbfe_bow_match, orbfe_bow_match_device, orbfe_bow_match_last_ms and
-                               * orbfe_bow_match_out only add entry points and a struct; find them by symbol */
+                               * orbfe_bow_match_out only add entry points and a struct; find them by symbol.
+                               * Likewise orbfe_tri_match, orbfe_tri_match_last_ms and orbfe_tri_match_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -560,6 +561,65 @@ int orbfe_bow_match(const uint8_t* desc32, const float* angle, const uint8_t* el
                     int32_t inclusive, double nnratio, const orbfe_bow_match_out* out, int64_t out_stride);
 /* Kernel time of the last orbfe_bow_match (ms, HIP events), for measurement. */
 int orbfe_bow_match_last_ms(float* ms);
+
+/* ---- matching many keyframe pairs for triangulation (ORBMatcher.search_for_triangulation, ORBMatcher.py:584-711) ----
+ *
+ * k_tri_match, one launch for n_pairs pairs (frame 1, frame 2) of one set of frames.  A frame is n descriptors, n
+ * float angles, n undistorted keypoint positions (x, y as doubles), n octaves, n flag bytes (below), a feature
+ * vector in orbfe_bow_match's CSR layout and two thresholds per pyramid level: thr_epi[l] (3.84 * mvLevelSigma2[l]
+ * in the reference) and thr_ex[l] (100 * mvScaleFactors[l]).  A pair adds F12 (9 doubles, row-major) and the
+ * epipole of frame 1's camera in frame 2 (ex, ey).
+ * The walk over the two feature vectors is the reference's own, done on the host inside the entry: every round
+ * draws one node from BOTH vectors; equal nodes are visited, otherwise one further node of the side with the
+ * smaller id is discarded.  (A node both frames hold can therefore go unvisited.)  Where that discard finds its
+ * vector exhausted the reference lets StopIteration escape: the pair gets stopped[p] = 1, no work, and its
+ * match12 row stays -1.
+ * Inside a visited node pair frame 1's run is walked in order.  A feature takes part iff its ORBFE_TRI_ELIGIBLE bit
+ * is set and, when only_stereo != 0, its ORBFE_TRI_STEREO bit too.  For i1, a candidate i2 of frame 2's run counts
+ * iff it takes part, is not yet matched in this pair, its Hamming distance d <= th, and, all in IEEE double in this
+ * operation order without contraction,
+ *   if neither feature has ORBFE_TRI_STEREO: (ex - x2) * (ex - x2) + (ey - y2) * (ey - y2) >= thr_ex[octave2];
+ *   a = x1 * F00 + y1 * F10 + F20, b = x1 * F01 + y1 * F11 + F21, c = x1 * F02 + y1 * F12 + F22,
+ *   num = a * x2 + b * y2 + c, den = a * a + b * b, den != 0 and num * num / den < thr_epi[octave2].
+ * i1 is matched to the counting candidate of the smallest d, on equal d the LAST in run order; there is no
+ * second-best ratio.  The winner is then blocked for the later i1 of the pair and the rotation bin is computed as
+ * for orbfe_bow_match.  Keeping the three fullest bins is left to the caller.
+ * The reference squares with `** 2` (libm pow), which may differ from a product by one ulp.  A pair in which any
+ * evaluated gate has |lhs - thr| <= thr * 2^-48 (the epipole gate is evaluated for every candidate that takes
+ * part, is unmatched and has d <= th when both features are mono; the line test for those that pass it), in which
+ * den is nonzero but below the smallest normal double, or in which a rotation bin falls outside [0, 30] gets
+ * ORBFE_TRI_MARGINAL in status[p]: its outputs are then this arithmetic's, and the caller that wants the
+ * reference's decision redoes the pair with the reference's own expressions.
+ * The longest frame taken is ORBFE_BOW_MAX_FRAME features.  Outputs per pair p (entries past n1 untouched):
+ *   match12[p * out_stride + i1] = i2 or -1    bin12[p * out_stride + i1] = rotation bin or -1
+ *   hist[p * 32 + b] = matches in bin b        n_raw[p] = matches      status[p], stopped[p]: one word per pair */
+#define ORBFE_TRI_ELIGIBLE 1 /* flag bit: the feature holds no map point            */
+#define ORBFE_TRI_STEREO 2   /* flag bit: the feature has a right coordinate (mvuRight >= 0) */
+#define ORBFE_TRI_MARGINAL 1 /* status bit: a decision of the pair lies within rounding of its threshold */
+typedef struct orbfe_tri_match_out {
+    int32_t* match12;
+    int8_t* bin12;
+    int32_t* hist;
+    int32_t* n_raw;
+    int32_t* status;  /* n_pairs words */
+    int32_t* stopped; /* n_pairs words */
+} orbfe_tri_match_out;
+/* Host buffers, synchronous.  Frame f is features [off[f], off[f + 1]) of desc32 / angle / xy (2 doubles each) /
+ * octave / flags; its nodes are entries [fv_off[f], fv_off[f + 1]) of fv_node / fv_end, its feature indices start at
+ * fv_idx[off[f]], its levels are entries [lvl_off[f], lvl_off[f + 1]) of thr_epi / thr_ex (all three offset arrays
+ * start at 0).  pairs: n_pairs x 2 frame indices; F12: n_pairs x 9; epipole: n_pairs x 2.  out_stride >= the longest
+ * frame 1 of the pairs.  Everything is validated before any device call, as for orbfe_bow_match, and also:
+ * ORBFE_EINVAL when an octave lies outside its frame's level table, or a coordinate, threshold, F12 or epipole is
+ * not finite (the message names the frame or pair), or th is outside [0, 256].  Process-wide buffers, stream and
+ * events of its own: concurrent callers take turns. */
+int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy, const int32_t* octave,
+                    const uint8_t* flags, const int64_t* off, int32_t n_frames, const int64_t* fv_off,
+                    const int32_t* fv_node, const int32_t* fv_end, const int32_t* fv_idx, const int64_t* lvl_off,
+                    const double* thr_epi, const double* thr_ex, const int32_t* pairs, const double* F12,
+                    const double* epipole, int32_t n_pairs, int32_t th, int32_t only_stereo,
+                    const orbfe_tri_match_out* out, int64_t out_stride);
+/* Kernel time of the last orbfe_tri_match (ms, HIP events), for measurement. */
+int orbfe_tri_match_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

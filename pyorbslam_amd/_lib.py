@@ -60,6 +60,15 @@ class BowMatchOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("match12", "match21", "bin12", "hist", "n_raw", "status")]
 
 
+ORBFE_TRI_ELIGIBLE, ORBFE_TRI_STEREO = 1, 2  # flag bits of orbfe_tri_match's per-feature byte
+ORBFE_TRI_MARGINAL = 1  # orbfe_tri_match status: a decision of the pair lies within rounding of its threshold
+
+
+class TriMatchOut(C.Structure):
+    """orbfe_tri_match_out: caller-owned output arrays of orbfe_tri_match."""
+    _fields_ = [(k, C.c_void_p) for k in ("match12", "bin12", "hist", "n_raw", "status", "stopped")]
+
+
 # cv::KeyPoint tuple layout (opencv_type_casters.h:106-108)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4")])
@@ -164,6 +173,9 @@ SIGNATURES = {
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                         C.POINTER(BowMatchOut), C.c_int64],
     "orbfe_bow_match_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_tri_match": [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_int32,
+                                                                            C.POINTER(TriMatchOut), C.c_int64],
+    "orbfe_tri_match_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -25,6 +25,12 @@ The replay loops restate ORBMatcher.py statement by statement on purpose: a drop
 reference's control flow, NumPy-2 dtype promotions and the order of its side effects exactly, so those
 lines necessarily read like the reference's.  The two tracking searches also have a native selection
 (orbfe_select_f_f / _f_p, host C) used when every compared value is a double.
+
+Three searches that the reference's callers run in a loop over candidates also exist for the whole list at
+once, one kernel launch and no host replay: search_by_BoW_kf_kf_many / search_by_BoW_kf_f_many (k_bow_match) and
+search_for_triangulation_many (k_tri_match).  Each returns what the loop of single searches returns; an element
+the kernels' arrays cannot express, or whose float64 decision lies within rounding of its threshold, takes the
+single search.
 """
 from __future__ import annotations
 
@@ -469,6 +475,134 @@ def _bow_frame(obj, kps, vp):
     f.fv_end = np.cumsum(lens).astype(np.int32)
     f.fv_idx = idx.astype(np.int32)
     return f
+
+
+def tri_match_arrays(desc, angle, xy, octave, flags, off, fv_off, fv_node, fv_end, fv_idx, lvl_off, thr_epi, thr_ex,
+                     pairs, F12, epipole, th=TH_LOW, only_stereo=False) -> dict:
+    """orbfe_tri_match (k_tri_match, include/orbfe.h): the match of ORBMatcher.search_for_triangulation
+    (ORBMatcher.py:584-711) for many keyframe pairs in one launch, before the rotation rejection.  Frame f is
+    features [off[f], off[f + 1]) of desc (x 32 u8) / angle (f32) / xy (x 2 f64) / octave (i32) / flags (u8:
+    ORBFE_TRI_ELIGIBLE | ORBFE_TRI_STEREO), its feature vector nodes [fv_off[f], fv_off[f + 1]) of fv_node / fv_end
+    with the indices at fv_idx[off[f]:], its levels [lvl_off[f], lvl_off[f + 1]) of thr_epi / thr_ex (f64); pairs:
+    (P, 2) frame indices, F12 (P, 3, 3) f64, epipole (P, 2) f64.  Returns match12 (P, stride) int32, bin12
+    (P, stride) int8, hist (P, 32), n_raw, status and stopped (P,); row p holds n1 entries, the rest stays -1."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    desc, angle, xy = arr(desc, np.uint8), arr(angle, np.float32), arr(xy, np.float64)
+    octave, flags = arr(octave, np.int32), arr(flags, np.uint8)
+    off, fv_off, lvl_off = arr(off, np.int64), arr(fv_off, np.int64), arr(lvl_off, np.int64)
+    fv_node, fv_end, fv_idx = arr(fv_node, np.int32), arr(fv_end, np.int32), arr(fv_idx, np.int32)
+    thr_epi, thr_ex = arr(thr_epi, np.float64), arr(thr_ex, np.float64)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    F12 = np.ascontiguousarray(F12, np.float64).reshape(-1, 9)
+    epipole = np.ascontiguousarray(epipole, np.float64).reshape(-1, 2)
+    n_frames, n_pairs = max(len(off) - 1, 0), len(pairs)
+    if len(F12) != n_pairs or len(epipole) != n_pairs:
+        raise ValueError("F12 / epipole do not cover the pairs")
+    n = int(off[-1]) if n_frames > 0 else 0
+    for a, per in ((desc, 32), (angle, 1), (xy, 2), (octave, 1), (flags, 1), (fv_idx, 1)):
+        if a is not None and a.size < n * per:
+            raise ValueError("a per-feature array is shorter than off[-1] features")
+    if n_frames > 0 and (len(fv_off) != n_frames + 1 or min(len(fv_node), len(fv_end)) < int(fv_off[-1])):
+        raise ValueError("fv_off / fv_node / fv_end do not cover the frames")
+    if n_frames > 0 and (len(lvl_off) != n_frames + 1 or min(len(thr_epi), len(thr_ex)) < int(lvl_off[-1])):
+        raise ValueError("lvl_off / thr_epi / thr_ex do not cover the frames")
+    stride = int(np.diff(off).max()) if n_frames > 0 else 0
+    m12 = np.full((n_pairs, stride), -1, np.int32)
+    b12 = np.full((n_pairs, stride), -1, np.int8)
+    hist = np.zeros((n_pairs, 32), np.int32)
+    n_raw = np.zeros(n_pairs, np.int32)
+    status = np.zeros(n_pairs, np.int32)
+    stopped = np.zeros(n_pairs, np.int32)
+    out = _lib.TriMatchOut(match12=m12.ctypes.data, bin12=b12.ctypes.data, hist=hist.ctypes.data,
+                           n_raw=n_raw.ctypes.data, status=status.ctypes.data, stopped=stopped.ctypes.data)
+    call("orbfe_tri_match", ptr(desc), ptr(angle), ptr(xy), ptr(octave), ptr(flags), ptr(off), n_frames, ptr(fv_off),
+         ptr(fv_node), ptr(fv_end), ptr(fv_idx), ptr(lvl_off), ptr(thr_epi), ptr(thr_ex), ptr(pairs), ptr(F12),
+         ptr(epipole), n_pairs, int(th), int(bool(only_stereo)), C.byref(out), stride)
+    return dict(match12=m12, bin12=b12, hist=hist, n_raw=n_raw, status=status, stopped=stopped)
+
+
+class _TriFrame:
+    __slots__ = ("desc", "angle", "xy", "xy_f32", "octave", "flags", "fv_node", "fv_end", "fv_idx", "thr_epi",
+                 "thr_ex")
+
+
+def _tri_frame(kf):
+    """Array form of a keyframe for k_tri_match: what _bow_frame gives for mvKeysUn, plus the undistorted
+    positions and octaves, the flag byte (ORBFE_TRI_ELIGIBLE: the slot holds nothing truthy, as
+    `not get_map_point(i)`; ORBFE_TRI_STEREO: mvuRight[i] >= 0) and the per-level thresholds
+    3.84 * mvLevelSigma2[l] and 100 * mvScaleFactors[l], evaluated as the reference writes them and then widened.
+    None when the arrays cannot express the keyframe (the caller then takes the single search): what _bow_frame
+    refuses, a coordinate that is not a double, an octave outside the level tables, a threshold that is not
+    finite, or lists of other lengths."""
+    kps = kf.mvKeysUn
+    vp = kf.get_map_point_matches()
+    f = _bow_frame(kf, kps, vp)
+    if f is None:
+        return None
+    n = len(f.desc)
+    ur = kf.mvuRight
+    if len(ur) != n:
+        return None
+    pts = [k.pt for k in kps]
+    xs, ys = [p[0] for p in pts], [p[1] for p in pts]
+    if not (set(map(type, xs)) <= _F64_SET and set(map(type, ys)) <= _F64_SET):
+        return None
+    xy = np.empty((n, 2), np.float64)
+    xy[:, 0], xy[:, 1] = xs, ys
+    if not np.isfinite(xy).all():
+        return None
+    octs = [k.octave for k in kps]
+    if not set(map(type, octs)) <= _INT_SET:
+        return None
+    octave = np.array(octs, np.int64)
+    sf, sig = kf.mvScaleFactors, kf.mvLevelSigma2
+    nl = min(len(sf), len(sig))
+    if n and (int(octave.min()) < 0 or int(octave.max()) >= nl):  # a negative octave indexes from the end
+        return None
+    try:
+        thr_ex = np.array([float(100 * sf[l]) for l in range(nl)], np.float64)
+        thr_epi = np.array([float(3.84 * sig[l]) for l in range(nl)], np.float64)
+    except (TypeError, ValueError):
+        return None
+    if not (np.isfinite(thr_ex).all() and np.isfinite(thr_epi).all()):
+        return None
+    t = _TriFrame()
+    t.desc, t.angle, t.fv_node, t.fv_end, t.fv_idx = f.desc, f.angle, f.fv_node, f.fv_end, f.fv_idx
+    t.xy, t.octave, t.thr_epi, t.thr_ex = xy, np.ascontiguousarray(octave, np.int32), thr_epi, thr_ex
+    t.xy_f32 = bool(np.array_equal(xy.astype(np.float32).astype(np.float64), xy))
+    free = np.fromiter(map(operator.not_, vp), bool, count=n)
+    stereo = _u_right(kf) >= 0
+    t.flags = (free * _lib.ORBFE_TRI_ELIGIBLE + stereo * _lib.ORBFE_TRI_STEREO).astype(np.uint8)
+    return t
+
+
+def _tri_epipole(ex, ey, f2):
+    """(ex, ey) as doubles when the epipole gate of search_for_triangulation (ORBMatcher.py:650-653) is decided by
+    k_tri_match's float64 arithmetic on the widened values, else None.  Doubles qualify as they are.  A float32
+    epipole (float32 poses) makes the reference evaluate the gate in float32: with float32-valued positions every
+    operation is then within 2^-24 relative of the double one, the whole left side within 2^-21, so the two agree
+    unless a mono feature of frame 2 has its left side within thr * 2^-20 of its threshold, which is checked here."""
+    vals = []
+    for v in (ex, ey):
+        if _is_f64(v):
+            vals.append((float(v.item() if type(v) is np.ndarray else v), True))
+        elif (type(v) is np.float32) or (type(v) is np.ndarray and v.dtype == np.float32 and v.size == 1):
+            vals.append((float(v.item() if type(v) is np.ndarray else v), False))
+        else:
+            return None
+    (x, xd), (y, yd) = vals
+    if not (np.isfinite(x) and np.isfinite(y)):
+        return None
+    if not (xd and yd):
+        if not f2.xy_f32:
+            return None
+        mono = (f2.flags & _lib.ORBFE_TRI_STEREO) == 0
+        lhs = (x - f2.xy[mono, 0]) * (x - f2.xy[mono, 0]) + (y - f2.xy[mono, 1]) * (y - f2.xy[mono, 1])
+        thr = f2.thr_ex[f2.octave[mono]]
+        if bool((np.abs(lhs - thr) <= thr * 2.0 ** -20).any()):
+            return None
+    return x, y
 
 
 class ORBMatcher:
@@ -1329,6 +1463,87 @@ class ORBMatcher:
         if den == 0:
             return False
         return (num ** 2) / den < 3.84 * pKF2.mvLevelSigma2[kp2.octave]
+
+    # ------------------------------------------------------------------------------------------------
+    # search_for_triangulation for many neighbours at once: one k_tri_match launch (orbfe_tri_match)
+
+    def search_for_triangulation_many(self, pKF1, kfs2, F12s, bOnlyStereo=False):
+        """[search_for_triangulation(pKF1, kf, F, bOnlyStereo) for kf, F in zip(kfs2, F12s)]
+        (LocalMapping.create_new_map_points' loop, LocalMapping.py:152-183), list for list, with one launch for the
+        whole list.  An element the arrays cannot express (_tri_frame, an F12 that is not a 3 x 3 float64 array,
+        an epipole _tri_epipole refuses) or that comes back ORBFE_TRI_MARGINAL takes the single search; where the
+        reference's walk lets StopIteration escape at element j, it is raised here after the elements before j."""
+        todo = list(zip(kfs2, F12s))
+        f1 = _tri_frame(pKF1)
+        frames, live, F, epi = [f1], [], [], []
+        for j, (kf, F12) in enumerate(todo):
+            if f1 is None:
+                break
+            if not (type(F12) is np.ndarray and F12.shape == (3, 3) and F12.dtype == _F64_DT
+                    and bool(np.isfinite(F12).all())):
+                continue
+            f2 = f1 if kf is pKF1 else _tri_frame(kf)
+            if f2 is None:
+                continue
+            # the epipole with the reference's own expressions (ORBMatcher.py:589-595)
+            Cw = pKF1.get_camera_center()
+            R2w = kf.get_rotation()
+            t2w = kf.get_translation()
+            C2 = R2w @ Cw + t2w
+            invz = 1.0 / C2[2]
+            ex = kf.fx * C2[0] * invz + kf.cx
+            ey = kf.fy * C2[1] * invz + kf.cy
+            e = _tri_epipole(ex, ey, f2)
+            if e is None:
+                continue
+            live.append(j)
+            frames.append(f2)
+            F.append(F12)
+            epi.append(e)
+        res = {}
+        if live:
+            off = np.zeros(len(frames) + 1, np.int64)
+            np.cumsum([len(f.desc) for f in frames], out=off[1:])
+            fv_off = np.zeros(len(frames) + 1, np.int64)
+            np.cumsum([len(f.fv_node) for f in frames], out=fv_off[1:])
+            lvl_off = np.zeros(len(frames) + 1, np.int64)
+            np.cumsum([len(f.thr_epi) for f in frames], out=lvl_off[1:])
+            cat = lambda k, dt: np.ascontiguousarray(np.concatenate([getattr(f, k) for f in frames]), dt)  # noqa: E731
+            fv_idx = np.zeros(int(off[-1]), np.int32)
+            for k, f in enumerate(frames):
+                fv_idx[off[k]:off[k] + len(f.fv_idx)] = f.fv_idx
+            r = tri_match_arrays(cat("desc", np.uint8).reshape(-1, 32), cat("angle", np.float32), cat("xy", np.float64),
+                                 cat("octave", np.int32), cat("flags", np.uint8), off, fv_off, cat("fv_node", np.int32),
+                                 cat("fv_end", np.int32), fv_idx, lvl_off, cat("thr_epi", np.float64),
+                                 cat("thr_ex", np.float64), [(0, k + 1) for k in range(len(live))], np.stack(F),
+                                 np.array(epi, np.float64), TH_LOW, bool(bOnlyStereo))
+            n1 = len(f1.desc)
+            for k, j in enumerate(live):
+                if r["stopped"][k]:
+                    res[j] = None
+                elif not r["status"][k]:
+                    res[j] = self._tri_reject(r["match12"][k, :n1], r["bin12"][k, :n1], r["hist"][k])
+        out = []
+        for j, (kf, F12) in enumerate(todo):
+            if j not in res:
+                out.append(self.search_for_triangulation(pKF1, kf, F12, bOnlyStereo))
+            elif res[j] is None:
+                raise StopIteration
+            else:
+                out.append(res[j])
+        return out
+
+    def _tri_reject(self, match12, bin12, hist):
+        """The rotation rejection and the result list of search_for_triangulation (ORBMatcher.py:679-696) over
+        k_tri_match's raw outputs: compute_three_maxima on the histogram, as the reference ranks it on this host."""
+        keep = match12 >= 0
+        if self.mbCheckOrientation:
+            kept = np.zeros(HISTO_LENGTH + 2, bool)
+            counts = [range(c) for c in hist[:HISTO_LENGTH].tolist()]
+            kept[np.asarray(self.compute_three_maxima(counts, HISTO_LENGTH))] = True
+            keep &= kept[bin12]
+        i1 = np.flatnonzero(keep)
+        return list(zip(i1.tolist(), match12[i1].tolist()))
 
     def _sim3_side(self, vpMapPoints, already, Rw, tw, sR, t, pKFo, th, K):
         """One direction of search_by_sim3 (ORBMatcher.py:744-783 / 785-825): best index in pKFo per point.
