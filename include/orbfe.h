@@ -38,7 +38,8 @@ extern "C" {
                                * orbfe_vocab_bow_last_ms (additive).  9: orbfe_get_stereo_bucket_kernel (additive).
                                * Still 9: orbfe_bow_match, orbfe_bow_match_device, orbfe_bow_match_last_ms and
                                * orbfe_bow_match_out only add entry points and a struct; find them by symbol.
-                               * Likewise orbfe_tri_match, orbfe_tri_match_last_ms and orbfe_tri_match_out */
+                               * Likewise orbfe_tri_match, orbfe_tri_match_last_ms and orbfe_tri_match_out, and
+                               * orbfe_fuse_search, orbfe_fuse_search_last_ms and orbfe_fuse_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -620,6 +621,74 @@ int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy,
                     const orbfe_tri_match_out* out, int64_t out_stride);
 /* Kernel time of the last orbfe_tri_match (ms, HIP events), for measurement. */
 int orbfe_tri_match_last_ms(float* ms);
+
+/* ---- fusing a list of map points into many keyframes (ORBMatcher.fuse_pkf_mp, ORBMatcher.py:482-582) ----
+ *
+ * k_fuse_search, one launch for every (keyframe k, point i) of n_kf keyframes and one shared list of n_pts map
+ * points: the search half of fuse_pkf_mp (:498-567).  Applying a match (:569-580) changes the map and stays with
+ * the caller, in the reference's order.
+ * Per keyframe: ORBFE_FUSE_KF_F64 doubles
+ *   [0..4] fx fy cx cy bf   [5..13] Rcw row-major   [14..16] tcw   [17..19] Ow   [20..23] mnMinX mnMaxX mnMinY mnMaxY
+ *   [24] mfGridElementWidthInv   [25] mfGridElementHeightInv   [26] mfLogScaleFactor
+ * (the pose values as the keyframe's getters return them, widened exactly), three ints (grid columns, grid rows,
+ * level count), n undistorted positions (x, y as doubles), n octaves, n right coordinates (negative: monocular;
+ * >= 0, so also 0.0: stereo), n descriptors, one entry per level of mvScaleFactors and mvInvLevelSigma2, and the
+ * grid as CSR: columns * rows + 1 offsets, cell (ix, iy) at ix * rows + iy, holding the entries of mGrid[ix][iy]
+ * in the stored order.  A feature that is in no cell is never a candidate.
+ * Per point: ORBFE_FUSE_PT_F64 doubles
+ *   [0..2] position   [3..5] normal   [6] get_min_distance_invariance()   [7] get_max_distance_invariance()
+ *   [8] mfMaxDistance
+ * and its descriptor.
+ * Per item, in IEEE double in this operation order without contraction (sums of three from the left):
+ *   pc = Rcw p + tcw; pc.z < 0: no candidate.  invz = 1 / pc.z (pc.z == 0 gives inf, and u, v below fail the image
+ *   test); u = fx * (pc.x * invz) + cx, v = fy * (pc.y * invz) + cy, ur = u - bf * invz;
+ *   mnMinX <= u < mnMaxX and mnMinY <= v < mnMaxY; PO = p - Ow, dist = sqrt(PO.PO) in [min, max] distance;
+ *   PO.normal >= 0.5 * dist; level = ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) clamped to [0, levels - 1];
+ *   r = th * scale[level]; the cell window floor(((u - mnMinX) - r) * widthInv) .. ceil(((u - mnMinX) + r) * widthInv)
+ *   (rows likewise), clamped, empty when it lies outside the grid (KeyFrame.get_features_in_area, KeyFrame.py:432-448).
+ * A candidate is an entry of the window's cells, visited column by column (ix outer, iy inner, the cell's stored
+ * order), with |x - u| < r and |y - v| < r, octave in [level - 1, level], and
+ *   stereo: ((u - x)^2 + (v - y)^2 + (ur - right)^2) * inv_sigma2[octave] <= 7.8
+ *   mono:   ((u - x)^2 + (v - y)^2) * inv_sigma2[octave] <= 5.99.
+ * The candidate of the smallest Hamming distance wins, among equal distances the earliest visited.
+ * Outputs at [k * out_stride + i], i < n_pts (entries past n_pts untouched): best_idx (feature index or -1),
+ * best_dist (Hamming distance or -1), status.
+ * The reference evaluates the same expressions in the dtypes of its operands (float32 poses and positions make the
+ * whole chain float32), squares through pow and takes another library's log.  Each compared value therefore
+ * carries an absolute bound on the reference's deviation, built from the magnitudes of the summed terms and
+ * scaled by eps (the unit of rounding the caller chooses from its dtypes).  status gets ORBFE_FUSE_MARGINAL when
+ * the bound could flip any decision taken for the item: the sign of pc.z, an image bound, the minimum or maximum
+ * distance, the viewing gate, the level quotient or a window bound near an integer, a visited entry's |dx| or
+ * |dy| near r, a chi-square near its threshold; also when an intermediate is not finite.  The outputs are then
+ * this arithmetic's, and the caller that wants the reference's decision redoes the item with the reference's own
+ * expressions.  The longest keyframe taken is ORBFE_BOW_MAX_FRAME features and as many grid entries; the point
+ * count is not limited.  A workgroup takes ORBFE_FUSE_CHUNK points of one keyframe. */
+#define ORBFE_FUSE_MARGINAL 1 /* status bit: a decision of the item lies within rounding of its threshold */
+#define ORBFE_FUSE_KF_F64 27
+#define ORBFE_FUSE_PT_F64 9
+#define ORBFE_FUSE_CHUNK 256
+typedef struct orbfe_fuse_out {
+    int32_t* best_idx;  /* n_kf x out_stride */
+    int32_t* best_dist; /* n_kf x out_stride */
+    uint8_t* status;    /* n_kf x out_stride */
+} orbfe_fuse_out;
+/* Host buffers, synchronous.  Keyframe k is features [off[k], off[k + 1]) of xy / octave / u_right / desc32, cell
+ * offsets [cell_at[k], cell_at[k + 1]) of cell_off (relative to the keyframe's first grid entry), grid entries
+ * [idx_at[k], idx_at[k + 1]) of cell_idx and levels [lvl_off[k], lvl_off[k + 1]) of scale / inv_sigma2 (all four
+ * offset arrays start at 0).  Everything is validated before any device call: ORBFE_EINVAL with a message for a null
+ * argument, offsets that decrease, a grid whose offset count is not columns * rows + 1 or whose last offset is not
+ * its entry count, a grid entry outside the keyframe's features, an octave outside the level table, a keyframe
+ * above the limit, an out_stride below n_pts, a level count <= 0 or not the level tables' length, a scalar that is
+ * not finite.  n_kf == 0 or n_pts == 0 launches nothing and succeeds.  Process-wide buffers, stream and events of
+ * its own: concurrent callers take turns. */
+int orbfe_fuse_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                      const int32_t* octave, const double* u_right, const uint8_t* desc32, const int64_t* cell_at,
+                      const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                      const double* scale, const double* inv_sigma2, int32_t n_kf, const double* pt_f64,
+                      const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const orbfe_fuse_out* out,
+                      int64_t out_stride);
+/* Kernel time of the last orbfe_fuse_search (ms, HIP events), for measurement. */
+int orbfe_fuse_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

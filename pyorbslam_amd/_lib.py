@@ -69,6 +69,15 @@ class TriMatchOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("match12", "bin12", "hist", "n_raw", "status", "stopped")]
 
 
+ORBFE_FUSE_MARGINAL = 1  # orbfe_fuse_search status: a decision of the item lies within rounding of its threshold
+ORBFE_FUSE_KF_F64, ORBFE_FUSE_PT_F64, ORBFE_FUSE_CHUNK = 27, 9, 256
+
+
+class FuseOut(C.Structure):
+    """orbfe_fuse_out: caller-owned output arrays of orbfe_fuse_search."""
+    _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
+
+
 # cv::KeyPoint tuple layout (opencv_type_casters.h:106-108)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4")])
@@ -176,6 +185,9 @@ SIGNATURES = {
     "orbfe_tri_match": [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_int32,
                                                                             C.POINTER(TriMatchOut), C.c_int64],
     "orbfe_tri_match_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_fuse_search": [C.c_void_p] * 14 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                              C.POINTER(FuseOut), C.c_int64],
+    "orbfe_fuse_search_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -30,7 +30,8 @@ Three searches that the reference's callers run in a loop over candidates also e
 once, one kernel launch and no host replay: search_by_BoW_kf_kf_many / search_by_BoW_kf_f_many (k_bow_match) and
 search_for_triangulation_many (k_tri_match).  Each returns what the loop of single searches returns; an element
 the kernels' arrays cannot express, or whose float64 decision lies within rounding of its threshold, takes the
-single search.
+single search.  fuse_pkf_mp_many (k_fuse_search) does the same for LocalMapping's fusion loops: one launch for
+the search of every (keyframe, point), then the matches applied on the host in the reference's order.
 """
 from __future__ import annotations
 
@@ -603,6 +604,186 @@ def _tri_epipole(ex, ey, f2):
         if bool((np.abs(lhs - thr) <= thr * 2.0 ** -20).any()):
             return None
     return x, y
+
+
+def fuse_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                       scale, inv_sigma2, pt_f64, pt_desc, th, eps) -> dict:
+    """orbfe_fuse_search (k_fuse_search, include/orbfe.h): the search half of ORBMatcher.fuse_pkf_mp
+    (ORBMatcher.py:498-567) for every (keyframe, point) in one launch.  kf_f64 (K, 27) and kf_i32 (K, 3) hold the
+    keyframes' scalars; keyframe k is features [off[k], off[k + 1]) of xy (x 2 f64) / octave (i32) / u_right (f64,
+    negative: mono) / desc (x 32 u8), cell offsets [cell_at[k], cell_at[k + 1]) of cell_off, grid entries
+    [idx_at[k], idx_at[k + 1]) of cell_idx and levels [lvl_off[k], lvl_off[k + 1]) of scale / inv_sigma2; pt_f64
+    (P, 9) and pt_desc (P, 32) are the points.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
+    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
+    kf_i32 = np.ascontiguousarray(kf_i32, np.int32).reshape(-1, 3)
+    pt_f64 = np.ascontiguousarray(pt_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
+    pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
+    off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
+    xy, u_right, scale, inv_sigma2 = (arr(a, np.float64) for a in (xy, u_right, scale, inv_sigma2))
+    octave, cell_off, cell_idx, desc = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32), arr(
+        desc, np.uint8)
+    n_kf, n_pts = len(kf_f64), len(pt_f64)
+    if len(kf_i32) != n_kf or len(pt_desc) != n_pts:
+        raise ValueError("kf_i32 / pt_desc do not cover the keyframes / points")
+    for a in (off, cell_at, idx_at, lvl_off):
+        if a is None or len(a) != n_kf + 1:
+            raise ValueError("an offset array does not have one entry per keyframe and one more")
+    if n_kf:
+        n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
+        for a, need in ((xy, 2 * n), (octave, n), (u_right, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni),
+                        (scale, nl), (inv_sigma2, nl)):
+            if need > 0 and (a is None or a.size < need):
+                raise ValueError("a per-keyframe array is shorter than its offsets say")
+    bi = np.full((n_kf, n_pts), -1, np.int32)
+    bd = np.full((n_kf, n_pts), -1, np.int32)
+    st = np.zeros((n_kf, n_pts), np.uint8)
+    out = _lib.FuseOut(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
+    call("orbfe_fuse_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(u_right), ptr(desc),
+         ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), ptr(inv_sigma2), n_kf,
+         ptr(pt_f64), ptr(pt_desc), n_pts, float(th), float(eps), C.byref(out), n_pts)
+    return dict(best_idx=bi, best_dist=bd, status=st)
+
+
+# eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
+# float32 (2^-24 is its unit roundoff) and the 2^-48 class of k_tri_match for float64
+FUSE_EPS_F32 = 2.0 ** -23
+FUSE_EPS_F64 = 2.0 ** -48
+_POSE_DT = (np.dtype(np.float32), np.dtype(np.float64))
+_F32_DT = np.dtype(np.float32)
+_TH_SET = frozenset((int, float, np.float64))
+_fuse_cache = weakref.WeakKeyDictionary()
+
+
+class _FuseFrame:
+    __slots__ = ("f64", "i32", "xy", "octave", "u_right", "desc", "cell_off", "cell_idx", "scale", "inv_sigma2", "f32",
+                 "pose")
+
+
+def _pose_part(a, shape):
+    """a as a flat list of doubles (widened exactly) and whether it was float32; None unless it is a finite
+    float32 / float64 array of that shape."""
+    if not (type(a) is np.ndarray and a.shape == shape and a.dtype in _POSE_DT and bool(np.isfinite(a).all())):
+        return None
+    return a.astype(np.float64).reshape(-1).tolist(), a.dtype == _F32_DT
+
+
+def _fuse_static(kf):
+    """(xy, octave, desc, cell_off, cell_idx) of a keyframe, cached while mvKeysUn, mDescriptors and mGrid are the
+    same objects; None for what the arrays cannot express."""
+    kps, descs, grid = kf.mvKeysUn, kf.mDescriptors, kf.mGrid
+    try:
+        ent = _fuse_cache.get(kf)
+    except TypeError:
+        ent = None
+    if ent is not None and ent[0] is kps and ent[1] is descs and ent[2] is grid and ent[3] == len(kps):
+        return ent[4]
+    n = len(kps)
+    cols, rows = kf.mnGridCols, kf.mnGridRows
+    if not (type(cols) in _INT_SET and type(rows) in _INT_SET and 0 < cols <= 4096 and 0 < rows <= 4096):
+        return None
+    if n > _lib.ORBFE_BOW_MAX_FRAME:
+        return None
+    if not (type(descs) is np.ndarray and descs.dtype == _U8_DT and descs.shape == (n, 32)):
+        return None
+    pts = [k.pt for k in kps]
+    xs, ys = [p[0] for p in pts], [p[1] for p in pts]
+    octs = [k.octave for k in kps]
+    if not (set(map(type, xs)) <= _F64_SET and set(map(type, ys)) <= _F64_SET and set(map(type, octs)) <= _INT_SET):
+        return None
+    xy = np.empty((n, 2), np.float64)
+    xy[:, 0], xy[:, 1] = xs, ys
+    if not np.isfinite(xy).all():
+        return None
+    if len(grid) != cols or any(len(col) != rows for col in grid):
+        return None
+    sizes = np.fromiter((len(cell) for col in grid for cell in col), np.int64, count=cols * rows)
+    total = int(sizes.sum())
+    if total > _lib.ORBFE_BOW_MAX_FRAME:
+        return None
+    flat = [g for col in grid for cell in col for g in cell]
+    if not set(map(type, flat)) <= _INT_SET:
+        return None
+    cell_idx = np.array(flat, np.int64).reshape(-1)
+    if total and (int(cell_idx.min()) < 0 or int(cell_idx.max()) >= n):  # a negative index counts from the end
+        return None
+    cell_off = np.zeros(cols * rows + 1, np.int32)
+    np.cumsum(sizes, out=cell_off[1:])
+    val = (xy, np.array(octs, np.int64).astype(np.int32).reshape(-1), np.ascontiguousarray(descs),
+           cell_off, cell_idx.astype(np.int32))
+    try:
+        _fuse_cache[kf] = (kps, descs, grid, n, val)
+    except TypeError:
+        pass
+    return val
+
+
+def _fuse_frame(kf):
+    """Array form of a keyframe for k_fuse_search: the scalars of include/orbfe.h's layout (the pose read anew on
+    every call, as its getters return it), the undistorted positions, octaves, right coordinates, descriptors,
+    level tables and the grid as CSR in the reference's visiting order.  None when the arrays cannot express the
+    keyframe (the caller then takes fuse_pkf_mp): intrinsics or grid parameters that are not plain doubles, a pose
+    that is not a finite float32 / float64 array of its shape, more features or grid entries than
+    ORBFE_BOW_MAX_FRAME, a keypoint field, mvuRight entry or level table entry of another type, an octave outside
+    the level tables."""
+    sc = (kf.fx, kf.fy, kf.cx, kf.cy, kf.mbf)
+    gr = (kf.mnMinX, kf.mnMaxX, kf.mnMinY, kf.mnMaxY, kf.mfGridElementWidthInv, kf.mfGridElementHeightInv,
+          kf.mfLogScaleFactor)
+    if not (set(map(type, sc)) <= _F64_SET and set(map(type, gr)) <= _F64_SET):
+        return None
+    levels = kf.mnScaleLevels
+    if type(levels) not in _INT_SET or levels <= 0:
+        return None
+    R, t, O = _pose_part(kf.get_rotation(), (3, 3)), _pose_part(kf.get_translation(), (3, 1)), _pose_part(
+        kf.get_camera_center(), (3, 1))
+    if R is None or t is None or O is None:
+        return None
+    st = _fuse_static(kf)
+    if st is None:
+        return None
+    xy, octave, desc, cell_off, cell_idx = st
+    n = len(xy)
+    sf, is2 = kf.mvScaleFactors, kf.mvInvLevelSigma2
+    if len(sf) < levels or len(is2) < levels:
+        return None
+    sf, is2 = list(sf[:levels]), list(is2[:levels])
+    if not (set(map(type, sf)) <= _F64_SET and set(map(type, is2)) <= _F64_SET):
+        return None
+    ur = kf.mvuRight
+    if len(ur) != n or not set(map(type, ur)) <= _UR_SET:
+        return None
+    u_right = _u_right(kf)
+    f64 = np.array(list(sc) + R[0] + t[0] + O[0] + list(gr), np.float64)
+    scale, inv_sigma2 = np.array(sf, np.float64), np.array(is2, np.float64)
+    if not (np.isfinite(f64).all() and np.isfinite(scale).all() and np.isfinite(inv_sigma2).all()
+            and np.isfinite(u_right).all()):
+        return None
+    if n and (int(octave.min()) < 0 or int(octave.max()) >= levels):
+        return None
+    f = _FuseFrame()
+    f.f64, f.i32 = f64, np.array([kf.mnGridCols, kf.mnGridRows, levels], np.int32)
+    f.xy, f.octave, f.u_right, f.desc, f.cell_off, f.cell_idx = xy, octave, u_right, desc, cell_off, cell_idx
+    f.scale, f.inv_sigma2 = scale, inv_sigma2
+    f.f32 = R[1] or t[1] or O[1]
+    return f
+
+
+def _fuse_point(pMP):
+    """(9 doubles, descriptor row, any float32) of a map point for k_fuse_search, or None when the arrays cannot
+    express it: a position or normal that is not a finite (3, 1) float32 / float64 array, distances that are not
+    plain doubles, a descriptor that is not 32 bytes of uint8."""
+    p, nrm = _pose_part(pMP.get_world_pos(), (3, 1)), _pose_part(pMP.get_normal(), (3, 1))
+    if p is None or nrm is None:
+        return None
+    d3 = (pMP.get_min_distance_invariance(), pMP.get_max_distance_invariance(), pMP.mfMaxDistance)
+    if not set(map(type, d3)) <= _F64_SET or not all(map(np.isfinite, d3)):
+        return None
+    d = pMP.get_descriptor()
+    if not (type(d) is np.ndarray and d.dtype == _U8_DT and d.size == 32):
+        return None
+    return p[0] + nrm[0] + list(d3), d.reshape(32), p[1] or nrm[1]
 
 
 class ORBMatcher:
@@ -1294,51 +1475,73 @@ class ORBMatcher:
                 n_fused += 1
         return n_fused, vpReplacePoint
 
+    def _fuse_cands(self, pKF, pMP, th, K):
+        """The search of fuse_pkf_mp for one point, up to the descriptor distances (ORBMatcher.py:498-560): the
+        candidates that pass the octave filter and the chi-square, in visiting order, or None when the point is
+        skipped before the candidates are read.  K: (fx, fy, cx, cy, bf, Rcw, tcw, Ow) of the keyframe."""
+        fx, fy, cx, cy, bf, Rcw, tcw, Ow = K
+        p3Dw = pMP.get_world_pos()
+        p3Dc = Rcw @ p3Dw + tcw
+        if p3Dc[2][0] < 0.0:
+            return None
+        invz = 1.0 / p3Dc[2][0]
+        x = p3Dc[0][0] * invz
+        y = p3Dc[1][0] * invz
+        u = fx * x + cx
+        v = fy * y + cy
+        ur = u - bf * invz
+        if not pKF.is_in_image(u, v):
+            return None
+        lvl = self._distance_gates(pMP, pKF, p3Dw, Ow)
+        if lvl is None:
+            return None
+        vIndices = pKF.get_features_in_area(u, v, th * pKF.mvScaleFactors[lvl])
+        if not vIndices:
+            return None
+        cands = []
+        for idx in vIndices:
+            kp = pKF.mvKeysUn[idx]
+            kpLevel = kp.octave
+            if kpLevel < lvl - 1 or kpLevel > lvl:
+                continue
+            if pKF.mvuRight[idx] >= 0:
+                ex, ey, er = u - kp.pt[0], v - kp.pt[1], ur - pKF.mvuRight[idx]
+                if (ex ** 2 + ey ** 2 + er ** 2) * pKF.mvInvLevelSigma2[kpLevel] > 7.8:
+                    continue
+            else:
+                ex, ey = u - kp.pt[0], v - kp.pt[1]
+                if (ex ** 2 + ey ** 2) * pKF.mvInvLevelSigma2[kpLevel] > 5.99:
+                    continue
+            cands.append(idx)
+        return cands
+
+    @staticmethod
+    def _fuse_apply(pKF, pMP, best_idx):
+        """ORBMatcher.py:570-579: what fuse_pkf_mp does with a point's best candidate."""
+        pMPinKF = pKF.get_map_point(best_idx)
+        if pMPinKF:
+            if not pMPinKF.is_bad():
+                if pMPinKF.observations() > pMP.observations():
+                    pMP.replace(pMPinKF)
+                else:
+                    pMPinKF.replace(pMP)
+        else:
+            pMP.add_observation(pKF, best_idx)
+            pKF.add_map_point(pMP, best_idx)
+
     # ORBMatcher.py:482-582
     def fuse_pkf_mp(self, pKF, vpMapPoints, th):
-        fx, fy, cx, cy, bf = pKF.fx, pKF.fy, pKF.cx, pKF.cy, pKF.mbf
-        Rcw = pKF.get_rotation()
-        tcw = pKF.get_translation()
-        Ow = pKF.get_camera_center()
+        K = (pKF.fx, pKF.fy, pKF.cx, pKF.cy, pKF.mbf, pKF.get_rotation(), pKF.get_translation(),
+             pKF.get_camera_center())
         work = []
         for pMP in vpMapPoints:
             # badness never reverts, so a point bad now is skipped by the replay as well; whether it is in
             # the keyframe can change during the search and is checked there
             if not pMP or pMP.is_bad():
                 continue
-            p3Dw = pMP.get_world_pos()
-            p3Dc = Rcw @ p3Dw + tcw
-            if p3Dc[2][0] < 0.0:
+            cands = self._fuse_cands(pKF, pMP, th, K)
+            if cands is None:
                 continue
-            invz = 1.0 / p3Dc[2][0]
-            x = p3Dc[0][0] * invz
-            y = p3Dc[1][0] * invz
-            u = fx * x + cx
-            v = fy * y + cy
-            ur = u - bf * invz
-            if not pKF.is_in_image(u, v):
-                continue
-            lvl = self._distance_gates(pMP, pKF, p3Dw, Ow)
-            if lvl is None:
-                continue
-            vIndices = pKF.get_features_in_area(u, v, th * pKF.mvScaleFactors[lvl])
-            if not vIndices:
-                continue
-            cands = []
-            for idx in vIndices:
-                kp = pKF.mvKeysUn[idx]
-                kpLevel = kp.octave
-                if kpLevel < lvl - 1 or kpLevel > lvl:
-                    continue
-                if pKF.mvuRight[idx] >= 0:
-                    ex, ey, er = u - kp.pt[0], v - kp.pt[1], ur - pKF.mvuRight[idx]
-                    if (ex ** 2 + ey ** 2 + er ** 2) * pKF.mvInvLevelSigma2[kpLevel] > 7.8:
-                        continue
-                else:
-                    ex, ey = u - kp.pt[0], v - kp.pt[1]
-                    if (ex ** 2 + ey ** 2) * pKF.mvInvLevelSigma2[kpLevel] > 5.99:
-                        continue
-                cands.append(idx)
             work.append((pMP, cands, pMP.get_descriptor()))
         dists = self._batched([(w[2], w[1]) for w in work], pKF.mDescriptors)
         n_fused = 0
@@ -1352,18 +1555,113 @@ class ORBMatcher:
                     best_dist = dist
                     best_idx = idx
             if best_dist <= TH_LOW:
-                pMPinKF = pKF.get_map_point(best_idx)
-                if pMPinKF:
-                    if not pMPinKF.is_bad():
-                        if pMPinKF.observations() > pMP.observations():
-                            pMP.replace(pMPinKF)
-                        else:
-                            pMPinKF.replace(pMP)
-                else:
-                    pMP.add_observation(pKF, best_idx)
-                    pKF.add_map_point(pMP, best_idx)
+                self._fuse_apply(pKF, pMP, best_idx)
                 n_fused += 1
         return n_fused
+
+    def _fuse_one(self, pKF, pMP, th, K):
+        """(best_dist, best_idx) of one point in one keyframe with the reference's own expressions on the objects
+        (ORBMatcher.py:498-567); the few distances are host popcounts.  (inf, -1) without a candidate."""
+        cands = self._fuse_cands(pKF, pMP, th, K)
+        best_dist, best_idx = float('inf'), -1
+        if cands:
+            d = pMP.get_descriptor()
+            for idx in cands:
+                dist = descriptor_distance(d, pKF.mDescriptors[idx])
+                if dist < best_dist:
+                    best_dist = dist
+                    best_idx = idx
+        return best_dist, best_idx
+
+    def fuse_pkf_mp_many(self, kfs, vpMapPoints, th):
+        """[fuse_pkf_mp(kf, vpMapPoints, th) for kf in kfs] (LocalMapping.search_in_neighbors' loops,
+        LocalMapping.py:359-360 and :375), value for value and side effect for side effect, with one k_fuse_search
+        launch for every (keyframe, point) of the call.  The points are read once: every point that is not None, not
+        bad and that the arrays can express (_fuse_point).  The replay then runs on the host in the reference's
+        order, keyframe by keyframe and point by point, with is_bad() and is_in_key_frame(kf) read at that moment,
+        and applies ORBMatcher.py:569-580 to the device's best candidate.  One item is redone alone with the
+        reference's expressions (_fuse_one) when it came back ORBFE_FUSE_MARGINAL, when its point is not
+        expressible, or when its point's descriptor is no longer the one that was sent (MapPoint.replace recomputes
+        the survivor's).  A keyframe _fuse_frame refuses takes fuse_pkf_mp whole at its place in the order, as does
+        every keyframe when th is not a plain number."""
+        kfs = list(kfs)
+        if not isinstance(vpMapPoints, (list, tuple)):
+            vpMapPoints = list(vpMapPoints)
+        if type(th) not in _TH_SET or not np.isfinite(th):
+            return [self.fuse_pkf_mp(kf, vpMapPoints, th) for kf in kfs]
+        frames = [_fuse_frame(kf) for kf in kfs]
+        live = [k for k, f in enumerate(frames) if f is not None]
+        # the points once: slot >= 0 is the row sent to the device, -1 not expressible, -2 None or bad already
+        slot, rows, descs, snaps, f32 = [], [], [], [], False
+        if live:
+            for pMP in vpMapPoints:
+                if not pMP or pMP.is_bad():
+                    slot.append(-2)
+                    continue
+                pt = _fuse_point(pMP)
+                if pt is None:
+                    slot.append(-1)
+                    continue
+                slot.append(len(rows))
+                rows.append(pt[0])
+                descs.append(pt[1])
+                f32 = f32 or pt[2]
+        res = None
+        if live and rows:
+            fr = [frames[k] for k in live]
+            f32 = f32 or any(f.f32 for f in fr)
+
+            def offs(lens):
+                o = np.zeros(len(fr) + 1, np.int64)
+                np.cumsum(lens, out=o[1:])
+                return o
+            cat = lambda name: np.concatenate([getattr(f, name) for f in fr])  # noqa: E731
+            pt_desc = np.stack(descs)
+            snaps = [d.tobytes() for d in descs]
+            res = fuse_search_arrays(np.stack([f.f64 for f in fr]), np.stack([f.i32 for f in fr]),
+                                     offs([len(f.xy) for f in fr]), cat("xy"), cat("octave"), cat("u_right"),
+                                     cat("desc"), offs([len(f.cell_off) for f in fr]), cat("cell_off"),
+                                     offs([len(f.cell_idx) for f in fr]), cat("cell_idx"),
+                                     offs([len(f.scale) for f in fr]), cat("scale"), cat("inv_sigma2"),
+                                     np.array(rows, np.float64), pt_desc, th,
+                                     FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+        slot_arr = np.array(slot, np.int64)
+        alone = np.flatnonzero(slot_arr == -1)   # list positions whose point goes alone in every keyframe
+        sent = np.flatnonzero(slot_arr >= 0)     # list positions in device row order
+        out = []
+        row = {k: j for j, k in enumerate(live)}
+        for k, kf in enumerate(kfs):
+            if frames[k] is None:
+                out.append(self.fuse_pkf_mp(kf, vpMapPoints, th))
+                continue
+            if res is None:
+                todo, bi, bd, st = alone, None, None, None
+            else:
+                j = row[k]
+                bi, bd, st = res["best_idx"][j], res["best_dist"][j], res["status"][j]
+                # an item without a candidate and without a marginal decision does nothing, whatever its
+                # descriptor has become; the others in list order
+                todo = np.sort(np.concatenate([alone, sent[(bi >= 0) | (st != 0)]]))
+                bi, bd, st = bi.tolist(), bd.tolist(), st.tolist()
+            K = None
+            n_fused = 0
+            for i in todo.tolist():
+                pMP = vpMapPoints[i]
+                if pMP.is_bad() or pMP.is_in_key_frame(kf):
+                    continue
+                s = slot[i]
+                if s >= 0 and not st[s] and pMP.get_descriptor().tobytes() == snaps[s]:
+                    best_dist, best_idx = bd[s], bi[s]
+                else:
+                    if K is None:
+                        K = (kf.fx, kf.fy, kf.cx, kf.cy, kf.mbf, kf.get_rotation(), kf.get_translation(),
+                             kf.get_camera_center())
+                    best_dist, best_idx = self._fuse_one(kf, pMP, th, K)
+                if best_idx >= 0 and best_dist <= TH_LOW:
+                    self._fuse_apply(kf, pMP, best_idx)
+                    n_fused += 1
+            out.append(n_fused)
+        return out
 
     @staticmethod
     def _triangulation_nodes(fv1, fv2):
