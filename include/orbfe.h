@@ -39,7 +39,9 @@ extern "C" {
                                * Still 9: orbfe_bow_match, orbfe_bow_match_device, orbfe_bow_match_last_ms and
                                * orbfe_bow_match_out only add entry points and a struct; find them by symbol.
                                * Likewise orbfe_tri_match, orbfe_tri_match_last_ms and orbfe_tri_match_out, and
-                               * orbfe_fuse_search, orbfe_fuse_search_last_ms and orbfe_fuse_out */
+                               * orbfe_fuse_search, orbfe_fuse_search_last_ms and orbfe_fuse_out, and
+                               * orbfe_kfdb_query_many, orbfe_kfdb_query_many_device, orbfe_kfdb_set_scratch_limit,
+                               * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -730,6 +732,60 @@ int orbfe_bow_score(const int32_t* q_word, const double* q_weight, int32_t nq, c
                     int32_t* common, int32_t* first, double* score);
 /* Kernel time of the last orbfe_kfdb_query (ms, HIP events; 0 for an empty database). */
 int orbfe_kfdb_last_ms(orbfe_kfdb_handle h, float* ms);
+
+/* ---- many queries in one launch, gated on the device (k_bow_score_many, k_bow_gate) ----
+ *
+ * n_query vectors against the whole database.  Per (query q, slot s) the same common / first / score as
+ * orbfe_kfdb_query gives for q alone, bit for bit.  Then, per query, the reference's word gate
+ * (KeyFrameDatabase.py:60-66, 126-131) on the device:
+ *   max_common[q] = the largest common over live slots that are not excluded for q (0 when there is none);
+ *   n_sharing[q]  = the live slots with common > 0, excluded ones included;
+ *   slot s is a hit iff it is live, not excluded for q, common > 0 and
+ *                       common > (int32_t)((double)max_common[q] * gate_ratio)
+ * (one IEEE double product, truncated: Python's int(max * 0.8); gate_ratio = 0 keeps every sharing slot).
+ * Query q's hits are written in ascending slot order to entries [q * hit_cap, q * hit_cap + min(n_hits[q],
+ * hit_cap)) of hit_slot / hit_common / hit_first / hit_score; n_hits[q] is always the true count, so
+ * n_hits[q] > hit_cap tells the caller to ask again with more room.  hit_cap = 0 writes no hit (the four arrays
+ * may be NULL).  Exclusions: query q's are excl_slot[excl_off[q] .. excl_off[q + 1]), ascending, distinct and
+ * below n_slots (the reference's connected set; for a batch also a frame's temporal neighbours); excl_off = NULL
+ * excludes nothing.  Dense rows: when common / first / score are given, row q (n_slots entries, excluded and
+ * erased slots included) goes to entry q * dense_stride of each; each of the three may be NULL.
+ * All buffers of *out are host memory; both entries are synchronous and run under the handle's mutex, like
+ * orbfe_kfdb_query.  The dense intermediate (16 B per (query, slot)) lives in device scratch owned by the handle:
+ * when it would exceed the scratch limit the queries go through the kernels in chunks, one query at the least,
+ * with identical results. */
+typedef struct orbfe_kfdb_many_out {
+    int32_t* n_sharing;   /* [n_query]                                                     */
+    int32_t* max_common;  /* [n_query]                                                     */
+    int32_t* n_hits;      /* [n_query] true count, may exceed hit_cap                      */
+    int32_t* hit_slot;    /* [n_query][hit_cap], ascending; entries past min(n_hits, hit_cap) unspecified */
+    int32_t* hit_common;  int32_t* hit_first;  double* hit_score;   /* the same layout     */
+    int32_t* common;  int32_t* first;  double* score;   /* dense [n_query][dense_stride]; each may be NULL */
+} orbfe_kfdb_many_out;
+/* Host queries: query q is entries [q_off[q], q_off[q + 1]) of q_word / q_weight (q_off[0] = 0, non-decreasing).
+ * Everything is validated before any device call: ORBFE_EINVAL unless every query's ids are distinct,
+ * non-negative and ascending, the offsets and exclusions are as above, gate_ratio lies in [0, 1) and
+ * hit_cap >= 0; ORBFE_ECAPACITY when a dense array is given and dense_stride < n_slots.  n_query = 0 or an
+ * empty database answers without touching the device (zeros in the three per-query arrays). */
+int orbfe_kfdb_query_many(orbfe_kfdb_handle h, const int64_t* q_off, const int32_t* q_word, const double* q_weight,
+                          int32_t n_query, const int64_t* excl_off, const int32_t* excl_slot, double gate_ratio,
+                          int32_t hit_cap, int64_t dense_stride, const orbfe_kfdb_many_out* out);
+/* Device-resident queries: query f is the n_words[f] entries from f * bow_stride of d_bow->bow_word / bow_weight
+ * (device pointers), exactly what orbfe_vocab_bow_device wrote with out_stride = bow_stride; the counts are read
+ * on the device and clamped to [0, bow_stride].  excl_*, *out and its arrays are host memory, checked as above.
+ * The call first uploads what the device copy of the database lacks, then runs on hip_stream (void* =
+ * hipStream_t), ordered after the work already enqueued there, synchronises that stream and returns with the
+ * results in the host buffers.  It allocates only when the scratch has to grow. */
+int orbfe_kfdb_query_many_device(orbfe_kfdb_handle h, const orbfe_bow_out* d_bow, int64_t bow_stride, int32_t n_query,
+                                 const int64_t* excl_off, const int32_t* excl_slot, double gate_ratio,
+                                 int32_t hit_cap, int64_t dense_stride, const orbfe_kfdb_many_out* out,
+                                 void* hip_stream);
+/* Upper bound in bytes (>= 0) of the dense intermediate of the many-query calls; the default is 64 MiB (4 Mi
+ * (query, slot) pairs).  A chunk always holds one query at the least, so n_slots * 16 B is the floor. */
+int orbfe_kfdb_set_scratch_limit(orbfe_kfdb_handle h, int64_t bytes);
+/* Kernel time of the last many-query call (both kernels, summed over its chunks; ms, HIP events; 0 when the
+ * call was answered without the device). */
+int orbfe_kfdb_many_last_ms(orbfe_kfdb_handle h, float* ms);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,12 @@ class FuseOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
 
 
+class KfdbManyOut(C.Structure):
+    """orbfe_kfdb_many_out: caller-owned host arrays of orbfe_kfdb_query_many / _many_device."""
+    _fields_ = [(k, C.c_void_p) for k in ("n_sharing", "max_common", "n_hits", "hit_slot", "hit_common", "hit_first",
+                                          "hit_score", "common", "first", "score")]
+
+
 # cv::KeyPoint tuple layout (opencv_type_casters.h:106-108)
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                      ("octave", "<i4")])
@@ -174,6 +180,12 @@ SIGNATURES = {
     "orbfe_bow_score": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "orbfe_kfdb_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
+    "orbfe_kfdb_query_many": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                              C.c_double, C.c_int32, C.c_int64, C.POINTER(KfdbManyOut)],
+    "orbfe_kfdb_query_many_device": [C.c_void_p, C.POINTER(BowOut), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_double, C.c_int32, C.c_int64, C.POINTER(KfdbManyOut), C.c_void_p],
+    "orbfe_kfdb_set_scratch_limit": [C.c_void_p, C.c_int64],
+    "orbfe_kfdb_many_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
     "orbfe_bow_match_device": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BowOut), C.c_int64, C.c_void_p,
                                C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(BowMatchOut), C.c_int64,

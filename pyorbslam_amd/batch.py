@@ -142,6 +142,27 @@ class StereoFrontEnd:
         return BowArrays(ints[0, :nw].copy(), b["weight"][i, :nw].cpu().numpy(), ints[1, :nn].copy(),
                          ints[2, :nn].copy(), ints[3, :nk].copy(), nk)
 
+    def query_bow(self, db, gate_ratio: float = 0.8, exclude=None, hit_cap=None, stream_ptr: int = 0,
+                  dense: bool = False):
+        """Ask the place-recognition database db (kfdb.BowDatabase) with every frame of the last bow(), on
+        stream_ptr (the stream bow() ran on): orbfe_kfdb_query_many_device reads the resident BoW vectors where
+        bow() left them, scores all frames against all slots in one launch, applies the word gate
+        common > int(max_common * gate_ratio) per frame on the device and brings back the surviving slots only.
+        exclude: per frame an iterable of slots (or None) that neither set the gate nor are reported, e.g. the
+        slots of the frame's temporal neighbours.  Returns one record per frame (kfdb.run_many): n_sharing,
+        max_common, n_hits and the hits' slot / common / first / score in ascending slot order; a frame without
+        words gets an empty record.  Synchronises stream_ptr."""
+        from .kfdb import run_many
+        if self._bow is None:
+            raise RuntimeError("query_bow needs the BoW vectors of a bow() call first")
+        n, out = self._bow_frames, self._bow["out"]
+
+        def launch(excl_off, excl_slot, ratio, cap, stride, res):
+            return _lib.lib().orbfe_kfdb_query_many_device(db._h, C.byref(out), self.kp_cap, n, excl_off, excl_slot,
+                                                           ratio, cap, stride, res, C.c_void_p(stream_ptr))
+
+        return run_many(db, n, launch, gate_ratio, exclude, hit_cap, dense)
+
     def match_bow(self, pairs, th: int = 50, inclusive: bool = False, nnratio: float = 1.0, eligible=None,
                   stream_ptr: int = 0) -> int:
         """Enqueue the BoW-guided match (k_bow_match, ORBMatcher.py:21-213 before the rotation rejection) of frame

@@ -53,15 +53,62 @@ constexpr int kBowMaxBlocks = 2048;   // 8 blocks per CU: a block loops over vec
 
 constexpr int kBowUnroll = 4;         // words per lane and pass: independent searches in flight per lane
 
-// One stored vector per wave.  Per pass of 64 * kBowUnroll words, lane j takes words j, j + 64, ... of the
-// pass and binary-searches the query for each (LDS copy when LDS is true, global otherwise).  The search is
-// the branchless halving form, whose trip count depends on nq alone: every lane runs the same steps, and the
-// kBowUnroll searches of a lane are independent, so their reads overlap instead of queueing behind one
-// another (the kernel is bound by that chain's latency).  Then, 64 words at a time in
-// ascending order: the ballot of the hits gives common and first; only hit lanes fetch the two weights and
-// form their term; the terms are added to the wave-uniform running sum in ascending lane order (= ascending
-// word id) by walking the ballot's set bits with a lane read, so the sum is the sequential one whatever the
-// chunking.
+// One pass of one stored vector against one query, the routine k_bow_score and k_bow_score_many share (so the
+// two agree bit for bit by construction).  w[u] is the stored word at position u * 64 + lane of the pass (-1 past
+// the vector's end: ids are non-negative, -1 matches nothing) and wt the pass's first weight.  Each lane
+// binary-searches the nq > 0 query ids q (LDS or global) for its kBowUnroll words.  The search is the
+// branchless halving form, whose trip count depends on nq alone: every lane runs the same steps, and the
+// kBowUnroll searches of a lane are independent, so their reads overlap instead of queueing behind one another
+// (the kernel is bound by that chain's latency).  Then, 64 words at a time in ascending
+// order: the ballot of the hits gives common and first; only hit lanes fetch the two weights and form their
+// term; the terms are added to the wave-uniform running sum in ascending lane order (= ascending word id) by
+// walking the ballot's set bits with a lane read, so the sum is the sequential one whatever the chunking.
+__device__ __forceinline__ void bow_pass(const int32_t* q, const double* __restrict__ q_weight, int nq,
+                                         const int (&w)[kBowUnroll], const double* __restrict__ wt, int lane,
+                                         int& common, int& first, double& sum) {
+    int base[kBowUnroll];
+#pragma unroll
+    for (int u = 0; u < kBowUnroll; ++u) base[u] = 0;
+    // q[base] ends as the last query id <= w (q[0] when there is none)
+    for (int n = nq; n > 1;) {
+        const int half = n >> 1;
+#pragma unroll
+        for (int u = 0; u < kBowUnroll; ++u) base[u] = q[base[u] + half] <= w[u] ? base[u] + half : base[u];
+        n -= half;
+    }
+#pragma unroll
+    for (int u = 0; u < kBowUnroll; ++u) {
+        const bool hit = q[base[u]] == w[u];
+        unsigned long long hits = __ballot(hit);
+        if (hits == 0) continue;
+        double term = 0.0;
+        if (hit) {
+            const double vi = q_weight[base[u]];
+            const double wi = wt[u * 64 + lane];
+            term = (fabs(vi - wi) - fabs(vi)) - fabs(wi);
+        }
+        if (first < 0) first = __shfl(w[u], __ffsll((long long)hits) - 1, 64);
+        common += __popcll(hits);
+        while (hits) {
+            const int b = __ffsll((long long)hits) - 1;
+            hits &= hits - 1;
+            sum += __shfl(term, b, 64);
+        }
+    }
+}
+
+// The stored words of one pass: lane j takes words j, j + 64, ... of the 64 * kBowUnroll words from position c.
+__device__ __forceinline__ void bow_load_pass(const int32_t* __restrict__ word, int64_t off, int c, int len, int lane,
+                                              int (&w)[kBowUnroll]) {
+#pragma unroll
+    for (int u = 0; u < kBowUnroll; ++u) {
+        const int j = c + u * 64 + lane;
+        w[u] = j < len ? word[off + j] : -1;
+    }
+}
+
+// One query, one stored vector per wave, passes of 64 * kBowUnroll words through bow_pass (query ids in LDS when
+// LDS is true, global otherwise).
 template <bool LDS>
 __global__ __launch_bounds__(64 * kBowWaves) void k_bow_score(const int32_t* __restrict__ q_word,
                                                               const double* __restrict__ q_weight, int nq,
@@ -86,45 +133,240 @@ __global__ __launch_bounds__(64 * kBowWaves) void k_bow_score(const int32_t* __r
         double sum = 0.0;
         const int len = (sl.live && nq > 0) ? sl.len : 0;
         for (int c = 0; c < len; c += 64 * kBowUnroll) {
-            int w[kBowUnroll], base[kBowUnroll];
-#pragma unroll
-            for (int u = 0; u < kBowUnroll; ++u) {
-                const int j = c + u * 64 + lane;
-                w[u] = j < len ? word[sl.off + j] : -1;  // ids are non-negative: -1 matches nothing
-                base[u] = 0;
-            }
-            // q[base] ends as the last query id <= w (q[0] when there is none)
-            for (int n = nq; n > 1;) {
-                const int half = n >> 1;
-#pragma unroll
-                for (int u = 0; u < kBowUnroll; ++u) base[u] = q[base[u] + half] <= w[u] ? base[u] + half : base[u];
-                n -= half;
-            }
-#pragma unroll
-            for (int u = 0; u < kBowUnroll; ++u) {
-                const bool hit = q[base[u]] == w[u];
-                unsigned long long hits = __ballot(hit);
-                if (hits == 0) continue;
-                double term = 0.0;
-                if (hit) {
-                    const double vi = q_weight[base[u]];
-                    const double wi = weight[sl.off + c + u * 64 + lane];
-                    term = (fabs(vi - wi) - fabs(vi)) - fabs(wi);
-                }
-                if (first < 0) first = __shfl(w[u], __ffsll((long long)hits) - 1, 64);
-                common += __popcll(hits);
-                while (hits) {
-                    const int b = __ffsll((long long)hits) - 1;
-                    hits &= hits - 1;
-                    sum += __shfl(term, b, 64);
-                }
-            }
+            int w[kBowUnroll];
+            bow_load_pass(word, sl.off, c, len, lane, w);
+            bow_pass(q, q_weight, nq, w, weight + sl.off + c, lane, common, first, sum);
         }
         if (lane == 0) {
             out_common[s] = common;
             out_first[s] = first;
             out_score[s] = -sum / 2.0;
         }
+    }
+}
+
+// ---- many queries in one launch ---------------------------------------------------------------------------------
+#ifdef ORBFE_BOW_TILE  // same-box A/B builds of other tile shapes
+constexpr int kBowTile = ORBFE_BOW_TILE;
+constexpr int kBowManyWaves = ORBFE_BOW_MANY_WAVES;
+#else
+constexpr int kBowTile = 4;        // queries whose word ids one block of k_bow_score_many stages in LDS
+constexpr int kBowManyWaves = 8;   // waves of that block: they share the staged tile, one stored vector per wave
+#endif                             // (4 x 8 by measurement)
+constexpr int kBowTileLdsWords = 16000;  // LDS budget of a tile: 62.5 KiB of dynamic LDS at the most, within the
+                                         // 64 KiB a launch gets without opting in, so two blocks still share a CU;
+                                         // a tile of four 1 500-word queries takes 23.4 KiB: six blocks fit and
+                                         // four of them fill the CU's 32 waves
+constexpr int kGateThreads = 1024;  // k_bow_gate: one block per query,
+constexpr int kGateItems = 4;       // consecutive slots per thread and step: 4 096 slots per compaction step
+static_assert(kBowTile >= 1 && kBowTile <= 64, "lane t of a wave keeps the running results of the tile's query t");
+static_assert(kBowManyWaves >= 1 && kBowManyWaves <= 16, "at most 1 024 threads per block");
+
+// Where the queries of a many-query call are.  Host entry: query g is entries [off[g], off[g + 1]) of word /
+// weight.  Device entry (off == nullptr): the count[g] entries from g * stride, what orbfe_vocab_bow_device
+// wrote; the count is clamped to [0, stride] here, on the device.
+struct BowQueries {
+    const int32_t* word;
+    const double* weight;
+    const int64_t* off;
+    const int32_t* count;
+    int64_t stride;
+};
+
+__device__ __forceinline__ void query_span(const BowQueries& qs, int g, int64_t& start, int& len) {
+    if (qs.off) {
+        start = qs.off[g];
+        len = (int)(qs.off[g + 1] - start);
+    } else {
+        start = (int64_t)g * qs.stride;
+        const int64_t n = qs.count[g];
+        len = (int)(n < 0 ? 0 : (n > qs.stride ? qs.stride : n));
+    }
+}
+
+// Queries [q0, q0 + n_query) against every stored vector: block (x, y) takes the tile of kBowTile queries from
+// q0 + y * kBowTile and the slots x * kBowManyWaves + wave, + gridDim.x * kBowManyWaves, ...  The tile's word ids
+// are staged in LDS once per block, packed one after the other: a query longer than kBowLdsWords, or one that
+// no longer fits in the launch's lds_words, is searched in global memory instead.  Per stored vector a wave loads
+// each pass of 64 * kBowUnroll words once and runs bow_pass on it for every query of the tile, so the arena is
+// streamed once per tile, not once per query.  The running common / first / sum of query t live in lane t
+// between passes (they are wave-uniform inside bow_pass).  Results go to out_*[(y * kBowTile + t) * n_slots + s].
+__global__ __launch_bounds__(64 * kBowManyWaves) void k_bow_score_many(
+    BowQueries qs, int q0, int n_query, int lds_words, const KfdbSlot* __restrict__ slot,
+    const int32_t* __restrict__ word, const double* __restrict__ weight, int64_t n_slots,
+    int32_t* __restrict__ out_common, int32_t* __restrict__ out_first, double* __restrict__ out_score) {
+    extern __shared__ int32_t s_q[];
+    __shared__ int64_t s_start[kBowTile];
+    __shared__ int s_len[kBowTile], s_at[kBowTile];  // s_at: where the query starts in s_q, -1 = not staged
+    const int t0 = blockIdx.y * kBowTile;
+    const int nt = min(kBowTile, n_query - t0);
+    if (threadIdx.x == 0) {
+        int used = 0;
+        for (int t = 0; t < nt; ++t) {
+            int64_t start;
+            int len;
+            query_span(qs, q0 + t0 + t, start, len);
+            s_start[t] = start;
+            s_len[t] = len;
+            const bool fits = len <= kBowLdsWords && used + len <= lds_words;
+            s_at[t] = fits ? used : -1;
+            if (fits) used += len;
+        }
+    }
+    __syncthreads();
+    for (int t = 0; t < nt; ++t)
+        if (s_at[t] >= 0)
+            for (int i = threadIdx.x; i < s_len[t]; i += blockDim.x) s_q[s_at[t] + i] = qs.word[s_start[t] + i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    for (int64_t s = (int64_t)blockIdx.x * kBowManyWaves + wave; s < n_slots;
+         s += (int64_t)gridDim.x * kBowManyWaves) {
+        const KfdbSlot sl = slot[s];
+        int my_common = 0, my_first = -1;  // lane t: query t of the tile
+        double my_sum = 0.0;
+        const int len = sl.live ? sl.len : 0;
+        for (int c = 0; c < len; c += 64 * kBowUnroll) {
+            int w[kBowUnroll];
+            bow_load_pass(word, sl.off, c, len, lane, w);
+            for (int t = 0; t < nt; ++t) {
+                const int nq = s_len[t];
+                if (nq == 0) continue;
+                int common = __shfl(my_common, t, 64), first = __shfl(my_first, t, 64);
+                double sum = __shfl(my_sum, t, 64);
+                const double* qv = qs.weight + s_start[t];
+                if (s_at[t] >= 0)
+                    bow_pass(s_q + s_at[t], qv, nq, w, weight + sl.off + c, lane, common, first, sum);
+                else
+                    bow_pass(qs.word + s_start[t], qv, nq, w, weight + sl.off + c, lane, common, first, sum);
+                if (lane == t) {
+                    my_common = common;
+                    my_first = first;
+                    my_sum = sum;
+                }
+            }
+        }
+        if (lane < nt) {
+            const int64_t o = (int64_t)(t0 + lane) * n_slots + s;
+            out_common[o] = my_common;
+            out_first[o] = my_first;
+            out_score[o] = -my_sum / 2.0;
+        }
+    }
+}
+
+// whether slot s is in the ascending list e[0 .. n)
+__device__ __forceinline__ bool excluded(const int32_t* __restrict__ e, int n, int s) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] < s) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && e[lo] == s;
+}
+
+// The word gate of KeyFrameDatabase.detect_*_candidates (KeyFrameDatabase.py:60-66, 126-131) and the compaction
+// of the survivors, one block per query of the chunk (row blockIdx.x of the dense arrays, query q0 + blockIdx.x
+// of the call).  Step 1 reduces max_common (live slots that are not excluded) and n_sharing (live slots with
+// common > 0) over the block.  Step 2 walks the slots in ascending order, kGateThreads * kGateItems at a time,
+// each thread kGateItems consecutive ones: a hit is a live, not excluded slot with common > 0 and
+// common > (int32_t)((double)max_common * gate_ratio); its place in the output is the count of hits before it,
+// from a scan over the block (shuffles inside a wave, the wave totals through LDS), so the order is ascending
+// slot whatever the scheduling.  Hits past hit_cap are counted, not written.
+__global__ __launch_bounds__(kGateThreads) void k_bow_gate(
+    const int32_t* __restrict__ common, const int32_t* __restrict__ first, const double* __restrict__ score,
+    const KfdbSlot* __restrict__ slot, int64_t n_slots, int q0, const int64_t* __restrict__ excl_off,
+    const int32_t* __restrict__ excl_slot, double gate_ratio, int hit_cap, int32_t* __restrict__ n_sharing,
+    int32_t* __restrict__ max_common, int32_t* __restrict__ n_hits, int32_t* __restrict__ hit_slot,
+    int32_t* __restrict__ hit_common, int32_t* __restrict__ hit_first, double* __restrict__ hit_score) {
+    constexpr int kWaves = kGateThreads / 64;
+    __shared__ int s_a[kWaves], s_b[kWaves];
+    const int q = q0 + blockIdx.x;
+    common += (int64_t)blockIdx.x * n_slots;
+    first += (int64_t)blockIdx.x * n_slots;
+    score += (int64_t)blockIdx.x * n_slots;
+    const int32_t* ex = nullptr;
+    int n_ex = 0;
+    if (excl_off) {
+        ex = excl_slot + excl_off[q];
+        n_ex = (int)(excl_off[q + 1] - excl_off[q]);
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+
+    int sharing = 0, mx = 0;
+    for (int64_t s = threadIdx.x; s < n_slots; s += kGateThreads) {
+        const int c = common[s];
+        if (c > 0 && slot[s].live) {
+            ++sharing;
+            if (!excluded(ex, n_ex, (int)s)) mx = max(mx, c);
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        sharing += __shfl_xor(sharing, d, 64);
+        mx = max(mx, __shfl_xor(mx, d, 64));
+    }
+    if (lane == 0) {
+        s_a[wave] = sharing;
+        s_b[wave] = mx;
+    }
+    __syncthreads();
+    sharing = 0;
+    mx = 0;
+    for (int i = 0; i < kWaves; ++i) {
+        sharing += s_a[i];
+        mx = max(mx, s_b[i]);
+    }
+    __syncthreads();  // s_a is reused below
+    const int gate = (int32_t)((double)mx * gate_ratio);
+
+    int64_t total = 0;  // hits before the current step
+    for (int64_t s0 = 0; s0 < n_slots; s0 += (int64_t)kGateThreads * kGateItems) {
+        const int64_t mine = s0 + (int64_t)threadIdx.x * kGateItems;
+        int c[kGateItems];
+        bool hit[kGateItems];
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < kGateItems; ++k) {
+            const int64_t s = mine + k;
+            c[k] = s < n_slots ? common[s] : 0;
+            hit[k] = c[k] > 0 && c[k] > gate && slot[s].live && !excluded(ex, n_ex, (int)s);
+            n += hit[k];
+        }
+        int incl = n;  // inclusive scan of n over the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) s_a[wave] = incl;
+        __syncthreads();
+        int before = 0, step = 0;
+        for (int i = 0; i < kWaves; ++i) {
+            const int v = s_a[i];
+            if (i < wave) before += v;
+            step += v;
+        }
+        __syncthreads();
+        int64_t at = total + before + incl - n;
+#pragma unroll
+        for (int k = 0; k < kGateItems; ++k) {
+            if (!hit[k]) continue;
+            if (at < hit_cap) {
+                const int64_t o = (int64_t)q * hit_cap + at;
+                hit_slot[o] = (int32_t)(mine + k);
+                hit_common[o] = c[k];
+                hit_first[o] = first[mine + k];
+                hit_score[o] = score[mine + k];
+            }
+            ++at;
+        }
+        total += step;
+    }
+    if (threadIdx.x == 0) {
+        n_sharing[q] = sharing;
+        max_common[q] = mx;
+        n_hits[q] = (int32_t)total;
     }
 }
 
@@ -177,6 +419,26 @@ struct BowScratch {
     }
 };
 
+constexpr int64_t kManyScratchDefault = 64LL << 20;  // default limit of the dense intermediate, bytes
+constexpr int64_t kManyRowBytes = 16;                // common + first + score of one (query, slot)
+constexpr int kManyMaxChunk = 1 << 16;               // queries per chunk at the most (grid y = tiles of a chunk)
+
+// Device scratch of the many-query calls.  up: one page-locked block for everything a call uploads, down: one for
+// everything but the dense arrays that it brings back; each travels in one copy.
+struct ManyScratch {
+    DevBuf<int32_t> d_common, d_first;
+    DevBuf<double> d_score;
+    DevBuf<char> d_up, d_down;
+    HostBuf<char> h_up, h_down;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t limit = kManyScratchDefault;
+    float last_ms = 0.f;
+    ~ManyScratch() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace orbfe
 
 struct orbfe_kfdb {
@@ -192,6 +454,7 @@ struct orbfe_kfdb {
     DevBuf<KfdbSlot> d_slot;
     int64_t up_words = 0, dirty_lo = 0, dirty_hi = 0;
     BowScratch sc;
+    ManyScratch many;
     // Tracking (relocalisation), LocalMapping (KeyFrame.set_bad_flag -> erase) and LoopClosing share one
     // database (System.py:45): everything above is guarded by this mutex
     std::mutex mu;
@@ -291,6 +554,171 @@ struct PairScorer {
 PairScorer& pair_scorer() {
     static PairScorer* p = new PairScorer;
     return *p;
+}
+
+// ---- many queries ---------------------------------------------------------------------------------------------
+struct ManyCall {  // what the two entries share
+    int32_t n_query;
+    const int64_t* excl_off;
+    const int32_t* excl_slot;
+    double gate_ratio;
+    int32_t hit_cap;
+    int64_t dense_stride;
+    const orbfe_kfdb_many_out* out;
+};
+
+struct HostQueries {
+    const int64_t* off;
+    const int32_t* word;
+    const double* weight;
+    int64_t total;
+};
+
+inline size_t pad8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+
+// Everything that can be refused, before any device call.  Returns false when the call is answered here: no
+// query, or an empty database (zeros).
+bool check_many(orbfe_kfdb& d, const ManyCall& a, const char* what) {
+    const std::string w(what);
+    const orbfe_kfdb_many_out* o = a.out;
+    if (!(a.gate_ratio >= 0.0 && a.gate_ratio < 1.0)) throw Error(ORBFE_EINVAL, w + ": gate_ratio must be in [0, 1)");
+    if (a.hit_cap < 0 || a.dense_stride < 0) throw Error(ORBFE_EINVAL, w + ": negative hit_cap or dense_stride");
+    if (a.n_query > 0) {
+        if (!o || !o->n_sharing || !o->max_common || !o->n_hits) throw Error(ORBFE_EINVAL, w + ": null result array");
+        if (a.hit_cap > 0 && (!o->hit_slot || !o->hit_common || !o->hit_first || !o->hit_score))
+            throw Error(ORBFE_EINVAL, w + ": null hit array");
+    }
+    const int64_t ns = (int64_t)d.slot.size();
+    if (a.excl_off && a.n_query > 0) {
+        if (a.excl_off[0] != 0) throw Error(ORBFE_EINVAL, w + ": excl_off[0] must be 0");
+        for (int32_t g = 0; g < a.n_query; ++g) {
+            const int64_t lo = a.excl_off[g], hi = a.excl_off[g + 1];
+            if (hi < lo || hi - lo > 0x7FFFFFFF) throw Error(ORBFE_EINVAL, w + ": excl_off must not descend");
+            if (hi > lo && !a.excl_slot) throw Error(ORBFE_EINVAL, w + ": null excl_slot");
+            for (int64_t i = lo; i < hi; ++i)
+                if (a.excl_slot[i] < 0 || a.excl_slot[i] >= ns || (i > lo && a.excl_slot[i] <= a.excl_slot[i - 1]))
+                    throw Error(ORBFE_EINVAL, w + ": excluded slots must ascend and lie below n_slots");
+        }
+    }
+    if (a.n_query > 0 && (o->common || o->first || o->score) && a.dense_stride < ns)
+        throw Error(ORBFE_ECAPACITY, w + ": dense rows are shorter than the slot table");
+    d.many.last_ms = 0.f;
+    if (a.n_query == 0) return false;
+    if (ns == 0) {
+        std::memset(o->n_sharing, 0, (size_t)a.n_query * sizeof(int32_t));
+        std::memset(o->max_common, 0, (size_t)a.n_query * sizeof(int32_t));
+        std::memset(o->n_hits, 0, (size_t)a.n_query * sizeof(int32_t));
+        return false;
+    }
+    return true;
+}
+
+// The device half of a many-query call, on `stream`; returns with the results in the host buffers of a.out.
+// hq != nullptr: the queries are uploaded (dq is ignored); otherwise dq names them on the device.  Queries go
+// through the kernels in chunks whose dense intermediate fits the handle's scratch limit (one query at the
+// least); a chunk's rows are copied out before the next chunk overwrites them, in stream order.
+void run_many(orbfe_kfdb& d, const HostQueries* hq, BowQueries dq, const ManyCall& a, int lds_words,
+              hipStream_t stream) {
+    ManyScratch& m = d.many;
+    const int64_t ns = (int64_t)d.slot.size();
+    const size_t nq = (size_t)a.n_query, cap = (size_t)a.hit_cap;
+    for (hipEvent_t& e : m.ev)
+        if (!e) HIPCK(hipEventCreate(&e));
+
+    // one upload: weights | q_off | excl_off | words | excl_slot
+    const size_t n_ex = a.excl_off ? (size_t)a.excl_off[nq] : 0;
+    const size_t b_wt = hq ? pad8((size_t)hq->total * sizeof(double)) : 0;
+    const size_t b_qo = hq ? (nq + 1) * sizeof(int64_t) : 0;
+    const size_t b_eo = a.excl_off ? (nq + 1) * sizeof(int64_t) : 0;
+    const size_t b_wd = hq ? pad8((size_t)hq->total * sizeof(int32_t)) : 0;
+    const size_t b_es = pad8(n_ex * sizeof(int32_t));
+    const size_t o_qo = b_wt, o_eo = o_qo + b_qo, o_wd = o_eo + b_eo, o_es = o_wd + b_wd, up = o_es + b_es;
+    if (up) {
+        m.h_up.ensure(up);
+        m.d_up.ensure(up);
+        if (hq) {
+            std::memcpy(m.h_up.p, hq->weight, (size_t)hq->total * sizeof(double));
+            std::memcpy(m.h_up.p + o_qo, hq->off, b_qo);
+            std::memcpy(m.h_up.p + o_wd, hq->word, (size_t)hq->total * sizeof(int32_t));
+        }
+        if (a.excl_off) {
+            std::memcpy(m.h_up.p + o_eo, a.excl_off, b_eo);
+            std::memcpy(m.h_up.p + o_es, a.excl_slot, n_ex * sizeof(int32_t));
+        }
+        HIPCK(hipMemcpyAsync(m.d_up.p, m.h_up.p, up, hipMemcpyHostToDevice, stream));
+    }
+    if (hq)
+        dq = BowQueries{(const int32_t*)(m.d_up.p + o_wd), (const double*)m.d_up.p, (const int64_t*)(m.d_up.p + o_qo),
+                        nullptr, 0};
+    const int64_t* d_eo = a.excl_off ? (const int64_t*)(m.d_up.p + o_eo) : nullptr;
+    const int32_t* d_es = a.excl_off ? (const int32_t*)(m.d_up.p + o_es) : nullptr;
+
+    // one download: hit_score | n_sharing | max_common | n_hits | hit_slot | hit_common | hit_first
+    const size_t o_int = nq * cap * sizeof(double);
+    const size_t down = o_int + (3 * nq + 3 * nq * cap) * sizeof(int32_t);
+    m.h_down.ensure(down);
+    m.d_down.ensure(down);
+    double* d_hscore = (double*)m.d_down.p;
+    int32_t* d_int = (int32_t*)(m.d_down.p + o_int);
+    int32_t *d_nsh = d_int, *d_max = d_int + nq, *d_nh = d_int + 2 * nq, *d_hslot = d_int + 3 * nq;
+    int32_t *d_hcommon = d_hslot + nq * cap, *d_hfirst = d_hcommon + nq * cap;
+
+    const int64_t fit = std::max<int64_t>(1, m.limit / (ns * kManyRowBytes));
+    const int chunk = (int)std::min<int64_t>(std::min<int64_t>(fit, a.n_query), kManyMaxChunk);
+    m.d_common.ensure((size_t)chunk * ns);
+    m.d_first.ensure((size_t)chunk * ns);
+    m.d_score.ensure((size_t)chunk * ns);
+
+    const orbfe_kfdb_many_out& o = *a.out;
+    float total_ms = 0.f;
+    for (int q0 = 0; q0 < a.n_query; q0 += chunk) {
+        const int n = std::min(chunk, a.n_query - q0);
+        const int tiles = (n + kBowTile - 1) / kBowTile;
+        const int64_t want = (ns + kBowManyWaves - 1) / kBowManyWaves;
+        const unsigned gx = (unsigned)std::min<int64_t>(want, std::max(1, kBowMaxBlocks / tiles));
+        HIPCK(hipEventRecord(m.ev[0], stream));
+        hipLaunchKernelGGL(k_bow_score_many, dim3(gx, tiles), dim3(64 * kBowManyWaves),
+                           (size_t)lds_words * sizeof(int32_t), stream, dq, q0, n, lds_words, d.d_slot.p, d.d_word.p,
+                           d.d_weight.p, ns, m.d_common.p, m.d_first.p, m.d_score.p);
+        HIPCK(hipGetLastError());
+        hipLaunchKernelGGL(k_bow_gate, dim3(n), dim3(kGateThreads), 0, stream, m.d_common.p, m.d_first.p, m.d_score.p,
+                           d.d_slot.p, ns, q0, d_eo, d_es, a.gate_ratio, a.hit_cap, d_nsh, d_max, d_nh, d_hslot,
+                           d_hcommon, d_hfirst, d_hscore);
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(m.ev[1], stream));
+        const auto rows_out = [&](void* dst, const void* src, size_t elem) {
+            if (!dst) return;
+            char* to = (char*)dst + (size_t)q0 * a.dense_stride * elem;
+            if (a.dense_stride == ns) {
+                HIPCK(hipMemcpyAsync(to, src, (size_t)n * ns * elem, hipMemcpyDeviceToHost, stream));
+            } else {
+                for (int r = 0; r < n; ++r)
+                    HIPCK(hipMemcpyAsync(to + (size_t)r * a.dense_stride * elem, (const char*)src + (size_t)r * ns * elem,
+                                         (size_t)ns * elem, hipMemcpyDeviceToHost, stream));
+            }
+        };
+        rows_out(o.common, m.d_common.p, sizeof(int32_t));
+        rows_out(o.first, m.d_first.p, sizeof(int32_t));
+        rows_out(o.score, m.d_score.p, sizeof(double));
+        if (q0 + n == a.n_query)
+            HIPCK(hipMemcpyAsync(m.h_down.p, m.d_down.p, down, hipMemcpyDeviceToHost, stream));
+        HIPCK(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIPCK(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
+        total_ms += ms;
+    }
+    m.last_ms = total_ms;
+
+    const int32_t* h_int = (const int32_t*)(m.h_down.p + o_int);
+    std::memcpy(o.n_sharing, h_int, nq * sizeof(int32_t));
+    std::memcpy(o.max_common, h_int + nq, nq * sizeof(int32_t));
+    std::memcpy(o.n_hits, h_int + 2 * nq, nq * sizeof(int32_t));
+    if (cap) {
+        std::memcpy(o.hit_score, m.h_down.p, nq * cap * sizeof(double));
+        std::memcpy(o.hit_slot, h_int + 3 * nq, nq * cap * sizeof(int32_t));
+        std::memcpy(o.hit_common, h_int + 3 * nq + nq * cap, nq * cap * sizeof(int32_t));
+        std::memcpy(o.hit_first, h_int + 3 * nq + 2 * nq * cap, nq * cap * sizeof(int32_t));
+    }
 }
 
 }  // namespace
@@ -426,6 +854,82 @@ int orbfe_bow_score(const int32_t* q_word, const double* q_weight, int32_t nq, c
         HIPCK(hipMemcpyAsync(p.d_slot.p, p.slot.data(), (size_t)n_vec * sizeof(KfdbSlot), hipMemcpyHostToDevice,
                              p.sc.stream));
         p.sc.run(q_word, q_weight, nq, p.d_slot.p, p.d_word.p, p.d_weight.p, n_vec, common, first, score);
+    });
+}
+
+int orbfe_kfdb_query_many(orbfe_kfdb_handle h, const int64_t* q_off, const int32_t* q_word, const double* q_weight,
+                          int32_t n_query, const int64_t* excl_off, const int32_t* excl_slot, double gate_ratio,
+                          int32_t hit_cap, int64_t dense_stride, const orbfe_kfdb_many_out* out) {
+    return guarded([&] {
+        if (!h) throw Error(ORBFE_EINVAL, "null handle");
+        if (n_query < 0 || (n_query > 0 && !q_off)) throw Error(ORBFE_EINVAL, "bad argument");
+        int64_t total = 0;
+        if (n_query > 0) {
+            if (q_off[0] != 0) throw Error(ORBFE_EINVAL, "q_off[0] must be 0");
+            for (int32_t g = 0; g < n_query; ++g) {
+                const int64_t len = q_off[g + 1] - q_off[g];
+                if (len < 0 || len > 0x7FFFFFFF) throw Error(ORBFE_EINVAL, "q_off must not descend");
+            }
+            total = q_off[n_query];
+            if (total > 0 && (!q_word || !q_weight)) throw Error(ORBFE_EINVAL, "null query arrays");
+            for (int32_t g = 0; g < n_query; ++g) {
+                const int64_t len = q_off[g + 1] - q_off[g];
+                check_vector(len ? q_word + q_off[g] : nullptr, len ? q_weight + q_off[g] : nullptr, (int32_t)len,
+                             "orbfe_kfdb_query_many");
+            }
+        }
+        std::lock_guard<std::mutex> lk(h->mu);
+        ManyCall a{n_query, excl_off, excl_slot, gate_ratio, hit_cap, dense_stride, out};
+        if (!check_many(*h, a, "orbfe_kfdb_query_many")) return;
+        // the LDS a tile needs: its queries packed one after the other, as the kernel packs them
+        int lds_words = 0;
+        for (int32_t g0 = 0; g0 < n_query; g0 += kBowTile) {
+            int used = 0;
+            for (int32_t g = g0; g < std::min(n_query, g0 + kBowTile); ++g) {
+                const int64_t len = q_off[g + 1] - q_off[g];
+                if (len <= kBowLdsWords && used + len <= kBowTileLdsWords) used += (int)len;
+            }
+            lds_words = std::max(lds_words, used);
+        }
+        sync_device(*h);
+        HostQueries hq{q_off, q_word, q_weight, total};
+        run_many(*h, &hq, BowQueries{}, a, lds_words, h->sc.stream);
+    });
+}
+
+int orbfe_kfdb_query_many_device(orbfe_kfdb_handle h, const orbfe_bow_out* d_bow, int64_t bow_stride, int32_t n_query,
+                                 const int64_t* excl_off, const int32_t* excl_slot, double gate_ratio,
+                                 int32_t hit_cap, int64_t dense_stride, const orbfe_kfdb_many_out* out,
+                                 void* hip_stream) {
+    return guarded([&] {
+        if (!h) throw Error(ORBFE_EINVAL, "null handle");
+        if (n_query < 0 || bow_stride < 0 || bow_stride > 0x7FFFFFFF) throw Error(ORBFE_EINVAL, "bad argument");
+        if (n_query > 0 && (!d_bow || !d_bow->n_words || (bow_stride > 0 && (!d_bow->bow_word || !d_bow->bow_weight))))
+            throw Error(ORBFE_EINVAL, "null BoW arrays");
+        std::lock_guard<std::mutex> lk(h->mu);
+        ManyCall a{n_query, excl_off, excl_slot, gate_ratio, hit_cap, dense_stride, out};
+        if (!check_many(*h, a, "orbfe_kfdb_query_many_device")) return;
+        sync_device(*h);
+        const int lds_words = (int)std::min<int64_t>(kBowTile * std::min<int64_t>(bow_stride, kBowLdsWords),
+                                                     kBowTileLdsWords);
+        run_many(*h, nullptr, BowQueries{d_bow->bow_word, d_bow->bow_weight, nullptr, d_bow->n_words, bow_stride}, a,
+                 lds_words, (hipStream_t)hip_stream);
+    });
+}
+
+int orbfe_kfdb_set_scratch_limit(orbfe_kfdb_handle h, int64_t bytes) {
+    return guarded([&] {
+        if (!h || bytes < 0) throw Error(ORBFE_EINVAL, "bad argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->many.limit = bytes;
+    });
+}
+
+int orbfe_kfdb_many_last_ms(orbfe_kfdb_handle h, float* ms) {
+    return guarded([&] {
+        if (!h || !ms) throw Error(ORBFE_EINVAL, "null argument");
+        std::lock_guard<std::mutex> lk(h->mu);
+        *ms = h->many.last_ms;
     });
 }
 

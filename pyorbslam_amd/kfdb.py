@@ -11,6 +11,12 @@ shares enough words.  Here every added keyframe's BoW vector is a slot of an orb
           control flow and side effects (mnLoopQuery / mnLoopWords / mLoopScore, mnRelocQuery / mnRelocWords /
           mRelocScore) and return the same candidate lists
 
+Many queries share one launch through BowDatabase.query_many / query_many_arrays (orbfe_kfdb_query_many:
+k_bow_score_many scores a tile of queries per block, k_bow_gate applies the word gate
+common > int(max_common * gate_ratio) per query on the device and compacts the survivors, so only those
+travel) and, for a batch whose BoW vectors are still on the device, batch.StereoFrontEnd.query_bow.
+KeyFrameDatabase.detect_*_candidates_many feed the same replay from one such call.
+
 Why the replay is equivalent.  The reference meets keyframes in first-appearance order of its walk: query words
 ascending (a BoW vector is an OrderedDict sorted by word id), and within one word's list in insertion order.
 That is slot order sorted by (first[s], s) over the slots with common[s] > 0.  Per keyframe the walk's
@@ -143,6 +149,73 @@ def replay_reloc(slot_kf, common, first, score, query_id):
     return _retain(acc, best_acc)
 
 
+HIT_CAP_FIRST = 256  # hits per query a many-query call makes room for when the caller names no hit_cap
+
+
+def _exclusions(exclude, n_query):
+    """Per-query iterables of slots (None = nothing) as the CSR pair (excl_off, excl_slot), each list ascending
+    and distinct."""
+    if exclude is None:
+        return None, None
+    if len(exclude) != n_query:
+        raise ValueError("exclude needs one entry per query")
+    lists = [np.unique(np.asarray([] if e is None else list(e), np.int64)) for e in exclude]
+    off = np.zeros(n_query + 1, np.int64)
+    np.cumsum([len(x) for x in lists], out=off[1:])
+    slots = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+    if len(slots) and (slots.min() < -2 ** 31 or slots.max() >= 2 ** 31):
+        raise ValueError("excluded slot out of range")
+    return off, np.ascontiguousarray(slots, np.int32)
+
+
+def run_many(db, n_query, launch, gate_ratio, exclude, hit_cap, dense):
+    """The host side of both many-query entries: result buffers, the call, the overflow rule, the records.
+    launch(excl_off, excl_slot, gate_ratio, hit_cap, dense_stride, out) makes the C call and returns its code.
+
+    One record (a dict) per query: n_sharing, max_common, n_hits (the true count) and the hits in ascending slot
+    order as the arrays slot / common / first / score, min(n_hits, hit_cap) long; with dense=True also
+    dense_common / dense_first / dense_score, what query_arrays returns for that query.  hit_cap=None starts
+    with room for HIT_CAP_FIRST hits per query and, when a query overflowed, asks once more with the largest
+    n_hits."""
+    if n_query == 0:
+        return []
+    off, slots = _exclusions(exclude, n_query)
+    auto, retried = hit_cap is None, False
+    cap = None if auto else int(hit_cap)
+    while True:
+        n = db.stats()["n_slots"]  # a concurrent add may grow the table before the call: ask again on ECAPACITY
+        if cap is None:
+            cap = min(n, HIT_CAP_FIRST)
+        per = np.zeros((3, n_query), np.int32)
+        hit_int = np.zeros((3, n_query, cap), np.int32)
+        hit_score = np.zeros((n_query, cap), np.float64)
+        common = first = score = None
+        if dense:
+            common = np.zeros((n_query, n), np.int32)
+            first = np.full((n_query, n), -1, np.int32)
+            score = np.zeros((n_query, n), np.float64)
+        out = _lib.KfdbManyOut(*(a.ctypes.data if a is not None and a.size else None for a in (
+            per[0], per[1], per[2], hit_int[0], hit_int[1], hit_int[2], hit_score, common, first, score)))
+        rc = launch(ptr(off), ptr(slots), float(gate_ratio), cap, n, C.byref(out))
+        if rc == _lib.ORBFE_ECAPACITY and dense:
+            continue
+        _lib.check("orbfe_kfdb_query_many", rc)
+        if auto and not retried and int(per[2].max()) > cap:
+            cap, retried = int(per[2].max()), True
+            continue
+        break
+    recs = []
+    for q in range(n_query):
+        k = min(int(per[2, q]), cap)
+        r = dict(n_sharing=int(per[0, q]), max_common=int(per[1, q]), n_hits=int(per[2, q]),
+                 slot=hit_int[0, q, :k].copy(), common=hit_int[1, q, :k].copy(), first=hit_int[2, q, :k].copy(),
+                 score=hit_score[q, :k].copy())
+        if dense:
+            r.update(dense_common=common[q], dense_first=first[q], dense_score=score[q])
+        recs.append(r)
+    return recs
+
+
 class BowDatabase:
     """Thin owner of an orbfe_kfdb handle: slots of BoW vectors and the one-launch query."""
 
@@ -205,6 +278,41 @@ class BowDatabase:
         call("orbfe_kfdb_last_ms", self._h, C.byref(ms))
         return float(ms.value)
 
+    def query_many_arrays(self, words, weights, gate_ratio=0.0, exclude=None, hit_cap=None, dense=False):
+        """Many queries in one launch (orbfe_kfdb_query_many), gated and compacted on the device: words / weights
+        are lists of arrays, one pair per query; exclude, when given, one iterable of slots (or None) per query.
+        Returns one record per query, see run_many."""
+        words = [np.ascontiguousarray(w, np.int32).ravel() for w in words]
+        weights = [np.ascontiguousarray(v, np.float64).ravel() for v in weights]
+        if len(words) != len(weights) or any(len(w) != len(v) for w, v in zip(words, weights)):
+            raise ValueError("word ids and weights differ in length")
+        n_query = len(words)
+        off = np.zeros(n_query + 1, np.int64)
+        np.cumsum([len(w) for w in words], out=off[1:])
+        word = np.concatenate(words) if n_query else np.zeros(0, np.int32)
+        weight = np.concatenate(weights) if n_query else np.zeros(0, np.float64)
+
+        def launch(excl_off, excl_slot, ratio, cap, stride, out):
+            return lib().orbfe_kfdb_query_many(self._h, ptr(off), ptr(word), ptr(weight), n_query, excl_off,
+                                               excl_slot, ratio, cap, stride, out)
+
+        return run_many(self, n_query, launch, gate_ratio, exclude, hit_cap, dense)
+
+    def query_many(self, bvs, gate_ratio=0.0, exclude=None, hit_cap=None, dense=False):
+        arrs = [bow_arrays(bv) for bv in bvs]
+        return self.query_many_arrays([a[0] for a in arrs], [a[1] for a in arrs], gate_ratio, exclude, hit_cap,
+                                      dense)
+
+    def set_scratch_limit(self, n_bytes: int) -> None:
+        """Upper bound of the many-query calls' dense intermediate on the device (16 B per (query, slot)); above
+        it a call runs in chunks of queries, with identical results."""
+        call("orbfe_kfdb_set_scratch_limit", self._h, int(n_bytes))
+
+    def last_many_kernel_ms(self) -> float:
+        ms = C.c_float()
+        call("orbfe_kfdb_many_last_ms", self._h, C.byref(ms))
+        return float(ms.value)
+
 
 class KeyFrameDatabase:
     def __init__(self, voc):
@@ -251,6 +359,26 @@ class KeyFrameDatabase:
         with self.mMutex:
             common, first, score = self._db.query(F.mBowVec)
             return replay_reloc(self._slot_kf, common, first, score, F.mnId)
+
+    # Many queries, one launch: the dense rows of one many-query call, then the same replay query by query, in
+    # order.  No database state feeds back into a query's arrays, so this equals the loop of single calls: the
+    # same lists and the same mn*Query / mn*Words / m*Score on every keyframe.
+    def detect_loop_candidates_many(self, kfs, min_scores):
+        kfs, min_scores = list(kfs), list(min_scores)
+        if len(kfs) != len(min_scores):
+            raise ValueError("one min_score per keyframe")
+        connected = [kf.get_connected_key_frames() for kf in kfs]
+        with self.mMutex:
+            recs = self._db.query_many([kf.mBowVec for kf in kfs], hit_cap=0, dense=True)
+            return [replay_loop(self._slot_kf, r["dense_common"], r["dense_first"], r["dense_score"], kf.mnId, c, ms)
+                    for kf, r, c, ms in zip(kfs, recs, connected, min_scores)]
+
+    def detect_relocalization_candidates_many(self, frames):
+        frames = list(frames)
+        with self.mMutex:
+            recs = self._db.query_many([f.mBowVec for f in frames], hit_cap=0, dense=True)
+            return [replay_reloc(self._slot_kf, r["dense_common"], r["dense_first"], r["dense_score"], f.mnId)
+                    for f, r in zip(frames, recs)]
 
     def last_kernel_ms(self) -> float:
         return self._db.last_kernel_ms()
