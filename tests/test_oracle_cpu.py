@@ -11,6 +11,7 @@ import pytest
 from conftest import GOLDEN, KITTI, EUROC, BF, FX, STEREO_CASES, golden_case_images
 from oracle import oracle as O
 from oracle import stereo_oracle
+from octree_definition import octree_py as _octree_py
 from pyorbslam_amd import synth
 
 
@@ -191,94 +192,6 @@ def test_gaussian_q8_kernel_from_definition():
 
 
 # ----------------------------------------------------------------------------------- octree
-class _Node:
-    __slots__ = ("keys", "x0", "y0", "x1", "y1", "nomore", "cid")
-
-
-def _octree_py(K, minX, maxX, minY, maxY, N, reverse_ties=False):
-    """DistributeOctTree (ORBextractor.cpp:539-762) on a Python list; ties by creation id (the careful phase
-    divides the most recently created of equal-size nodes first), or with reverse_ties the oldest first — a
-    second admissible heap-address order."""
-    if not K:
-        return []
-    nIni = int(math.floor(np.float32(maxX - minX) / np.float32(maxY - minY) + np.float32(0.5)))
-    hX = np.float32(np.float32(maxX - minX) / np.float32(nIni))
-    ctr = [0]
-
-    def mk(keys, x0, y0, x1, y1):
-        n = _Node()
-        n.keys, n.x0, n.y0, n.x1, n.y1, n.nomore = keys, x0, y0, x1, y1, len(keys) == 1
-        n.cid = ctr[0]
-        ctr[0] += 1
-        return n
-
-    ini = [mk([], int(np.float32(hX * np.float32(i))), 0, int(np.float32(hX * np.float32(i + 1))), maxY - minY)
-           for i in range(nIni)]
-    for i, k in enumerate(K):
-        ini[int(np.float32(np.float32(k[0]) / hX))].keys.append(i)
-    nodes = []
-    for n in ini:
-        if n.keys:
-            n.nomore = len(n.keys) == 1
-            nodes.append(n)
-
-    def divide(n):
-        hx, hy = (n.x1 - n.x0 + 1) // 2, (n.y1 - n.y0 + 1) // 2
-        mx, my = n.x0 + hx, n.y0 + hy
-        parts = [[], [], [], []]
-        for i in n.keys:
-            parts[(0 if K[i][0] < mx else 1) + (0 if K[i][1] < my else 2)].append(i)
-        boxes = [(n.x0, n.y0, mx, my), (mx, n.y0, n.x1, my), (n.x0, my, mx, n.y1), (mx, my, n.x1, n.y1)]
-        return [(parts[q], boxes[q]) for q in range(4)]
-
-    while True:
-        prev = len(nodes)
-        front, keep, expand = [], [], []
-        for n in nodes:
-            if n.nomore:
-                keep.append(n)
-                continue
-            for keys, b in divide(n):
-                if keys:
-                    c = mk(keys, *b)
-                    front.insert(0, c)
-                    if len(keys) > 1:
-                        expand.append(c)
-        nodes = front + keep
-        if len(nodes) >= N or len(nodes) == prev:
-            break
-        if len(nodes) + 3 * len(expand) > N:
-            while True:
-                prev = len(nodes)
-                todo = sorted(expand, key=lambda n: (len(n.keys), -n.cid if reverse_ties else n.cid))
-                expand = []
-                done = False
-                for n in reversed(todo):
-                    kids = []
-                    for keys, b in divide(n):
-                        if keys:
-                            c = mk(keys, *b)
-                            kids.insert(0, c)
-                            if len(keys) > 1:
-                                expand.append(c)
-                    nodes.remove(n)
-                    nodes = kids + nodes
-                    if len(nodes) >= N:
-                        done = True
-                        break
-                if done or len(nodes) >= N or len(nodes) == prev:
-                    break
-            break
-    out = []
-    for n in nodes:
-        best = n.keys[0]
-        for i in n.keys[1:]:
-            if K[i][2] > K[best][2]:
-                best = i
-        out.append(K[best])
-    return out
-
-
 @pytest.mark.parametrize("seed", range(8))
 def test_octree_oracle_vs_python(seed):
     rng = np.random.default_rng(seed)
