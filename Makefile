@@ -9,7 +9,8 @@ SRC := pyorbslam_amd/csrc/orbfe_kernels.hip pyorbslam_amd/csrc/orbfe_host.hip py
        pyorbslam_amd/csrc/orbfe_trimatch.hip pyorbslam_amd/csrc/orbfe_fuse.hip
 CSRC := pyorbslam_amd/csrc/orbfe_png.cpp
 HDR := pyorbslam_amd/csrc/orbfe_common.h pyorbslam_amd/csrc/orbfe_kernels.h pyorbslam_amd/csrc/orbfe_host_util.h include/orbfe.h \
-       pyorbslam_amd/csrc/brief_pattern.inc pyorbslam_amd/csrc/brief_distinct.inc
+       pyorbslam_amd/csrc/brief_pattern.inc pyorbslam_amd/csrc/brief_distinct.inc \
+       pyorbslam_amd/csrc/brief_slot_order.inc
 LIB := pyorbslam_amd/_lib/liborbfe.so
 OBJ := $(patsubst pyorbslam_amd/csrc/%.hip,pyorbslam_amd/_lib/%.o,$(SRC)) \
        $(patsubst pyorbslam_amd/csrc/%.cpp,pyorbslam_amd/_lib/%.o,$(CSRC))

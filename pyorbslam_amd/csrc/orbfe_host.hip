@@ -613,7 +613,13 @@ std::vector<uint32_t> orb_tables(const int* umax) {
         for (int col = -18; col <= 18; ++col)
             if (row * row + col * col <= R * R)
                 for (int k = 0; k < 7; ++k) need[row + 18 + k][col + 21] = true;
-    int n = 0;
+    // Item lane + 64 k is lane's k-th: the 32 lanes of a half-wave read their items' source dwords 24 m + gx
+    // (+ 0, 1, 2, 12, 13, 14) together, LDS bank (24 m + gx) mod 32.  Every bank holds 5 to 8 of the 189 items, so
+    // no order of the six 32-lane groups is conflict-free; the r-th item of a bank (row-major) goes to group
+    // min(r, 5): groups 0 .. 4 hold one item of every bank and read without a conflict, and the collisions no
+    // order can avoid share group 5 (tools/orb_lds_model.py: 48 instead of 72 LDS cycles per keypoint).
+    int n = 0, in_bank[32] = {};
+    std::vector<std::pair<int, int>> groups[6];
     for (int m = 0; m < 22; ++m)
         for (int gx = 0; gx < 10; ++gx) {
             bool any = false;
@@ -621,14 +627,45 @@ std::vector<uint32_t> orb_tables(const int* umax) {
                 for (int c = 0; c < 4; ++c) any |= need[2 * m + rr][4 * gx + c];
             if (!any) continue;
             if (n >= 192) throw Error(ORBFE_EINVAL, "k_orb: more than 192 horizontal items");
-            t[n++] = (uint32_t)(2 * m * 12 + gx) | ((uint32_t)(m * 10 + gx) << 16);
+            ++n;
+            groups[std::min(in_bank[(2 * m * 12 + gx) % 32]++, 5)].push_back({m, gx});
         }
     // lanes without an item run a dummy one: source dword 0, H slot (row pair 0, group 0) — a corner of the
     // window no BRIEF sample reaches, so k_orb needs no per-item test
     for (int rr = 0; rr < 2; ++rr)
         for (int c = 0; c < 4; ++c)
             if (need[rr][c]) throw Error(ORBFE_EINVAL, "k_orb: the dummy H slot lies on the sample disc");
-    for (; n < 192; ++n) t[n] = 0u;
+    // inside a group: runs of 8 lanes (one LDS cycle of the b128 H store each) whose stores go to distinct banks
+    // 4 q .. 4 q + 3, q = (2 m + gx) mod 8, as far as a first-fit pass finds them; the group's dummies last
+    auto item = [](const std::pair<int, int>& it) {
+        return (uint32_t)(2 * it.first * 12 + it.second) | ((uint32_t)(it.first * 10 + it.second) << 16);
+    };
+    for (int g = 0; g < 6; ++g) {
+        std::vector<std::pair<int, int>>& left = groups[g];
+        if (left.size() > 32) throw Error(ORBFE_EINVAL, "k_orb: more than 32 horizontal items left for the last group");
+        uint32_t* out = t.data() + 32 * g;
+        const uint32_t* end = out + 32;
+        while (!left.empty()) {
+            int run = 0;
+            bool used[8] = {};
+            for (size_t i = 0; i < left.size() && run < 8;) {
+                const int q = (2 * left[i].first + left[i].second) % 8;
+                if (used[q]) {
+                    ++i;
+                    continue;
+                }
+                used[q] = true;
+                *out++ = item(left[i]);
+                left.erase(left.begin() + i);
+                ++run;
+            }
+            for (; run < 8 && !left.empty(); ++run) {
+                *out++ = item(left[0]);
+                left.erase(left.begin());
+            }
+        }
+        for (; out < end; ++out) *out = 0u;
+    }
     uint32_t* cw = t.data() + 192;
     int sl = 0;
     for (int r = 0; r < 31; ++r) {

@@ -26,18 +26,41 @@
 namespace orbfe {
 
 // The steered-BRIEF pattern by distinct sample point (brief_distinct.inc, generated from brief_pattern.inc):
-// 375 of its 512 ends are distinct.  c_points: (x, y) of the 384 slots as floats, slots 2 t and 2 t + 1 in one
-// 16-byte entry t; c_bit_slots: per descriptor bit, slot of (x0, y0) | slot of (x1, y1) << 16.
+// 375 of its 512 ends are distinct, in 384 slots.  k_orb takes them in the order of brief_slot_order.inc
+// (position -> slot, a permutation chosen against LDS bank conflicts: tools/orb_lds_model.py), composed here at
+// compile time.  c_points: (x, y) of the points at the 384 positions as floats, positions 2 t and 2 t + 1 in one
+// 16-byte entry t; c_bit_slots: per descriptor bit, position of (x0, y0) | position of (x1, y1) << 16.
 constexpr int kBriefSlots = 384;
 #define BRIEF_POINT(x, y) x, y,
 #define BRIEF_BIT(s0, s1)
-__constant__ __attribute__((aligned(16))) float c_points[2 * kBriefSlots] = {
+constexpr float kBriefSlotXY[2 * kBriefSlots] = {
 #include "brief_distinct.inc"
 };
 #undef BRIEF_POINT
 #undef BRIEF_BIT
+#define BRIEF_SLOT(s) s,
+constexpr int kBriefSlotOrder[kBriefSlots] = {
+#include "brief_slot_order.inc"
+};
+#undef BRIEF_SLOT
+constexpr int brief_slot_pos(int slot) {  // the position that holds `slot`; kBriefSlots if none does
+    int p = 0;
+    while (p < kBriefSlots && kBriefSlotOrder[p] != slot) ++p;
+    return p;
+}
+constexpr bool brief_slot_order_is_permutation() {
+    for (int s = 0; s < kBriefSlots; ++s)
+        if (brief_slot_pos(s) == kBriefSlots) return false;
+    return true;
+}
+static_assert(brief_slot_order_is_permutation(), "brief_slot_order.inc: every slot at exactly one position");
+#define BRIEF_SLOT(s) kBriefSlotXY[2 * (s)], kBriefSlotXY[2 * (s) + 1],
+__constant__ __attribute__((aligned(16))) float c_points[2 * kBriefSlots] = {
+#include "brief_slot_order.inc"
+};
+#undef BRIEF_SLOT
 #define BRIEF_POINT(x, y)
-#define BRIEF_BIT(s0, s1) (s0) | (s1) << 16,
+#define BRIEF_BIT(s0, s1) (uint32_t)brief_slot_pos(s0) | (uint32_t)brief_slot_pos(s1) << 16,
 __constant__ uint32_t c_bit_slots[256] = {
 #include "brief_distinct.inc"
 };
@@ -2920,11 +2943,16 @@ __device__ __forceinline__ int reflect101c(int p, int n) {  // reflect-101, clam
 //  * horizontal taps: the 189 (row pair, 4-column group) items the disc needs (a per-lane table), 10 v_dot4
 //    with shifted byte weights per row, stored row-pair interleaved as u16 pairs (dword = (H[2m][c], H[2m+1][c]));
 //  * BRIEF: a sample's blurred value depends on its pattern point and the angle only, and 375 of the
-//    pattern's 512 ends are distinct, so every distinct point is evaluated once: lane j evaluates slots
-//    2 (j + 64 i), + 1 (i = 0..2; 384 slots, the last 9 are the window centre and unused), each from its
-//    vertical taps in 4 interleaved dwords (2 ds_read2) with 4 v_dot2 whose weights depend on the sample
+//    pattern's 512 ends are distinct, so every distinct point is evaluated once: lane j evaluates positions
+//    2 (j + 64 i), + 1 (i = 0..2; 384 positions, 9 of them hold the window centre and are unused), each from
+//    its vertical taps in 4 interleaved dwords (2 ds_read2) with 4 v_dot2 whose weights depend on the sample
 //    row's parity, and leaves the blurred bytes in a per-wave LDS buffer; lane j then reads the two ends
 //    of its bits j + 64 i (i = 0..3) back from per-lane constant addresses; one ballot per 64 bits.
+//    Which point sits at which position is brief_slot_order.inc's: the 32 points a half-wave gathers
+//    together form a compact patch of the disc, which is compact at every angle and so spreads over H's banks
+//    (about 2 dwords on the fullest bank, 3.3 for scattered points), and the ends a half-wave reads back
+//    together lie on distinct banks of the byte buffer.
+//  The per-lane tables of the horizontal items are ordered against bank conflicts too (orb_tables).
 constexpr int kSrcRows = 43, kSrcDw = 12;
 constexpr int kHPairs = 22, kHGrp = 10, kHDw = 4 * kHGrp;  // H: 22 row pairs x 40 columns (dwords)
 constexpr int kOrbHItems = 3;          // horizontal items per lane (189 of 192 used)
@@ -2959,8 +2987,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
                                                     uint8_t* __restrict__ out_desc, int* __restrict__ out_count,
                                                     const uint32_t* __restrict__ tab, int gx, StereoArgs sa, int n_bucket) {
     static_assert(64 * WAVES >= kBriefSlots / 2, "one thread per s_pts entry");
-    __shared__ float4 s_pts[kBriefSlots / 2];              // (x, y) of slots 2 t, 2 t + 1
-    __shared__ uint16_t s_val[WAVES][kBriefSlots / 2];     // blurred bytes of slots 2 t | 2 t + 1 << 8
+    __shared__ float4 s_pts[kBriefSlots / 2];              // (x, y) of positions 2 t, 2 t + 1
+    __shared__ uint16_t s_val[WAVES][kBriefSlots / 2];     // blurred bytes of positions 2 t | 2 t + 1 << 8
     __shared__ uint2 s_cw[64 * kOrbCSlots];                // centroid slot: signed byte weights (u, v)
     __shared__ uint32_t s_src[WAVES][kSrcRows * kSrcDw];  // staged unblurred window
     __shared__ uint32_t s_h[WAVES][kHPairs * kHDw];       // horizontal taps, row-pair interleaved u16
@@ -3049,7 +3077,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
         const uint32_t src_a = (uint32_t)(uintptr_t)(lds_w32*)src, hb_a = (uint32_t)(uintptr_t)(lds_w32*)hb;
         const uint32_t val_a = (uint32_t)(uintptr_t)(lds_w16*)s_val[wid];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {  // slot s's byte is byte s of the wave's buffer
+        for (int i = 0; i < 4; ++i) {  // position p's byte is byte p of the wave's buffer
             bend1[i] = val_a + (bend0[i] >> 16);
             bend0[i] = val_a + (bend0[i] & 0xFFFFu);
             // opaque, or the compiler keeps the packed table words and re-adds (8 SDWA adds per keypoint)
@@ -3212,11 +3240,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(5)))
     const uint32_t kc = (uint32_t)(uintptr_t)(lds_u32*)hb + (uint32_t)(4 * (9 * kHDw + 21)) -
                         (uint32_t)(4 * kHDw) * 0xA00000u - (__float_as_uint(12582912.0f) << 2);
     //      Every distinct sample point once (c_points): phase 1 leaves the blurred bytes of the wave's 384
-    //      slots in val (s < 2^24, so the byte is byte 2 of s: one v_perm packs an iteration's two into one
+    //      positions in val (s < 2^24, so the byte is byte 2 of s: one v_perm packs an iteration's two into one
     //      16-bit store); after one wave_sync_lds, phase 2 compares the two ends of the lane's four bits from
     //      them.  val is written after the previous BRIEF's phase 2 read it: BRIEF(B)'s stores come after the
     //      wave_sync_lds in front of H(B) (BRIEF(A)'s val reads were waited before its ballots), and the next
-    //      pair's BRIEF(A) after the wave_sync_lds of its stage().  The pad slots (0, 0) read H at the window
+    //      pair's BRIEF(A) after the wave_sync_lds of its stage().  The pad positions (0, 0) read H at the window
     //      centre, which the disc's items cover, and no bit reads their bytes.
     typedef __attribute__((address_space(3))) uint16_t lds_v16;
     typedef __attribute__((address_space(3))) const uint8_t lds_v8;
