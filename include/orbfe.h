@@ -41,7 +41,8 @@ extern "C" {
                                * Likewise orbfe_tri_match, orbfe_tri_match_last_ms and orbfe_tri_match_out, and
                                * orbfe_fuse_search, orbfe_fuse_search_last_ms and orbfe_fuse_out, and
                                * orbfe_kfdb_query_many, orbfe_kfdb_query_many_device, orbfe_kfdb_set_scratch_limit,
-                               * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out */
+                               * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out, and orbfe_scw_search,
+                               * orbfe_scw_search_last_ms and orbfe_scw_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -691,6 +692,47 @@ int orbfe_fuse_search(const double* kf_f64, const int32_t* kf_i32, const int64_t
                       int64_t out_stride);
 /* Kernel time of the last orbfe_fuse_search (ms, HIP events), for measurement. */
 int orbfe_fuse_search_last_ms(float* ms);
+
+/* ---- loop closing's Sim3 projection searches (ORBMatcher.fuse_kf_scw_mp, ORBMatcher.py:395-480, and
+ *      ORBMatcher.search_by_projection_ckf_scw_mp, :850-922) ----
+ *
+ * k_scw_search, one launch for every (keyframe k, point i) of n_kf keyframes, each with a pose of its own, and one
+ * shared list of n_pts map points: the search half of both functions (:409-468 and :863-916).  What is done with
+ * the best candidate (:470-478, :918-920) and the TH_LOW test stay with the caller, in the reference's order.
+ * The keyframe block is orbfe_fuse_search's, ORBFE_FUSE_KF_F64 doubles in the same slots, so one packing serves
+ * both; slot [4] (bf) is not read and may hold anything, and the pose slots [5..19] hold Rcw, tcw and Ow as the
+ * caller got them from the Sim3 (sRcw / s, t / s, -Rcw^T tcw), widened exactly.  There are no right coordinates and
+ * no inverse sigma squares.  The point block and the grid are orbfe_fuse_search's.
+ * Per item the arithmetic is orbfe_fuse_search's up to the cell window, without ur.  The depth gate is pc.z < 0;
+ * at pc.z == 0 the division gives inf, u and v fail the image test, and the item ends without a candidate, which is
+ * also what the ckf search's pc.z <= 0 gives, so one path serves both.
+ * A candidate is an entry of the window's cells, visited column by column (ix outer, iy inner, the cell's stored
+ * order), whose blocked byte is 0 (blocked: one byte per feature, concatenated at `off` like the octaves; NULL:
+ * nothing is blocked), with |x - u| < r and |y - v| < r and octave in [level - 1, level].  There is no chi-square.
+ * The candidate of the smallest Hamming distance wins, among equal distances the earliest visited.  Taking
+ * candidates away never changes the order of those that remain: the winner over a smaller blocked set stands for
+ * every larger one that leaves it free.
+ * Outputs at [k * out_stride + i], i < n_pts (entries past n_pts untouched): best_idx (feature index or -1),
+ * best_dist (Hamming distance or -1), status.  status gets ORBFE_FUSE_MARGINAL under orbfe_fuse_search's bounds,
+ * scaled by eps: the sign of pc.z, an image bound, the minimum or maximum distance, the viewing gate, the level
+ * quotient or a window bound near an integer, a visited entry's |dx| or |dy| near r (a blocked entry marks
+ * nothing); also when an intermediate is not finite.  The limits are orbfe_fuse_search's. */
+typedef struct orbfe_scw_out {
+    int32_t* best_idx;  /* n_kf x out_stride */
+    int32_t* best_dist; /* n_kf x out_stride */
+    uint8_t* status;    /* n_kf x out_stride */
+} orbfe_scw_out;
+/* Host buffers, synchronous; the arrays and the checks are orbfe_fuse_search's (ORBFE_EINVAL with a message before
+ * any device call; slot [4] of a keyframe block is exempt from the finiteness check), n_kf == 0 or n_pts == 0
+ * launches nothing and succeeds.  Process-wide buffers, stream and events of its own: concurrent callers take
+ * turns. */
+int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                     const int32_t* octave, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+                     const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                     const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                     double th, double eps, const orbfe_scw_out* out, int64_t out_stride);
+/* Kernel time of the last orbfe_scw_search (ms, HIP events), for measurement. */
+int orbfe_scw_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

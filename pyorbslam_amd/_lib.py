@@ -78,6 +78,11 @@ class FuseOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
 
 
+class ScwOut(C.Structure):
+    """orbfe_scw_out: caller-owned output arrays of orbfe_scw_search."""
+    _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
+
+
 class KfdbManyOut(C.Structure):
     """orbfe_kfdb_many_out: caller-owned host arrays of orbfe_kfdb_query_many / _many_device."""
     _fields_ = [(k, C.c_void_p) for k in ("n_sharing", "max_common", "n_hits", "hit_slot", "hit_common", "hit_first",
@@ -200,6 +205,9 @@ SIGNATURES = {
     "orbfe_fuse_search": [C.c_void_p] * 14 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                               C.POINTER(FuseOut), C.c_int64],
     "orbfe_fuse_search_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_scw_search": [C.c_void_p] * 13 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
+                                             C.POINTER(ScwOut), C.c_int64],
+    "orbfe_scw_search_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None
@@ -290,6 +298,20 @@ def build_id() -> str:
     """SHA-256 prefix of the sources the loaded library was built from (orbfe_build_id)."""
     fn = getattr(lib(), "orbfe_build_id", None)
     return fn().decode() if fn is not None else "unknown"
+
+
+_device_present: bool | None = None
+
+
+def device_present() -> bool:
+    """Whether the HIP runtime the library is linked against sees a device; asked once (hipGetDeviceCount, reached
+    through the library's own dependency, so nothing else is loaded)."""
+    global _device_present
+    if _device_present is None:
+        n = C.c_int(0)
+        fn = getattr(lib(), "hipGetDeviceCount", None)
+        _device_present = fn is not None and fn(C.byref(n)) == 0 and n.value > 0
+    return _device_present
 
 
 def gpu_available() -> bool:

@@ -1,0 +1,440 @@
+// orbfe_scw.hip — the search half of LoopClosing's two Sim3 projection searches, ORBMatcher.fuse_kf_scw_mp
+// (ORBMatcher.py:395-480) and ORBMatcher.search_by_projection_ckf_scw_mp (:850-922), for every (keyframe, map point)
+// of a call in one launch on gfx950.
+//
+// Both project a list of map points into a keyframe with the pose a Sim3 gives (the caller divides the scale out on
+// the host, with the reference's expressions), gate each point (depth sign, image bounds, scale-invariance
+// distances, viewing angle), predict its pyramid level, search the keyframe's grid in a window of radius
+// th * scale[level] (KeyFrame.get_features_in_area, KeyFrame.py:432-460), keep the candidates whose octave is the
+// level or one below, and take the candidate of the smallest Hamming distance; among equal distances the EARLIEST
+// in visiting order (column ix outer, row iy inner, the cell's list as stored) wins.  This is k_fuse_search
+// (orbfe_fuse.hip) without the chi-square on the reprojection error and without the right coordinate, and with one
+// more input: a byte per feature that takes the feature out of the candidates (the ckf search skips a feature whose
+// vpMatched slot is taken).  A blocked entry is skipped first: it decides nothing, so it marks nothing either.
+//
+// The depth gate: fuse_kf_scw_mp skips z < 0, the ckf search z <= 0.  At z == 0 the first runs on to 1 / 0, u and v
+// become inf or NaN and fail the image test, so both skip the point and one code path serves both.
+//
+// k_scw_search: a workgroup is (keyframe, chunk of kScChunk points).  Phase 1: thread t does point t's geometry in
+// IEEE double (-ffp-contract=off, correctly rounded division and square root) and leaves u, v, their error bounds,
+// the radius, the level and the clamped cell window in LDS.  Phase 2: groups of kScGroup lanes take the chunk's
+// points in turn; for one column ix the window's cells are one contiguous range of the grid's CSR, whose entries the
+// lanes take kScGroup at a time.  A lane's key is dist << 16 | position in the keyframe's CSR (all ones without a
+// candidate); the __shfl_xor minimum over the group is the smallest distance and among equals the earliest visited.
+//
+// Every compared value carries the absolute bound of k_fuse_search on how far the reference's value can lie from
+// it, scaled by `eps`; a decision within its bound marks the item ORBFE_FUSE_MARGINAL and the caller redoes it with
+// the reference's expressions.  The derivation is in DESIGN.md under k_fuse_search.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "orbfe_host_util.h"
+
+using namespace orbfe;
+
+namespace orbfe {
+
+constexpr int kScChunk = ORBFE_FUSE_CHUNK;  // points per workgroup, one thread each in phase 1
+constexpr int kScGroup = 16;                // lanes that share one point's candidates in phase 2
+constexpr unsigned kScNone = 0xFFFFFFFFu;
+constexpr int kScKfF64 = ORBFE_FUSE_KF_F64;
+constexpr int kScPtF64 = ORBFE_FUSE_PT_F64;
+
+struct ScKfs {
+    const double* f64;   // kScKfF64 per keyframe
+    const int32_t* i32;  // cols, rows, levels per keyframe
+    const int64_t *off, *cell_at, *idx_at, *lvl_off;
+    const double *xy, *scale;
+    const int32_t *octave, *cell_off, *cell_idx;
+    const uint8_t *desc, *blocked;  // blocked: null when nothing is
+};
+
+struct ScPts {
+    const double* f64;  // kScPtF64 per point
+    const uint8_t* desc;
+    int64_t n;
+};
+
+struct ScOut {
+    int32_t *best_idx, *best_dist;
+    uint8_t* status;
+    int64_t stride;
+};
+
+// every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
+// is this one exactly
+__device__ __forceinline__ bool sc_near_int(double a, double e) { return fabs(a - rint(a)) < e; }
+
+__global__ __launch_bounds__(kScChunk) void k_scw_search(ScKfs kf, ScPts pt, double th, double eps, ScOut out) {
+    __shared__ double s_u[kScChunk], s_v[kScChunk], s_eu[kScChunk], s_ev[kScChunk], s_r[kScChunk];
+    __shared__ int16_t s_x0[kScChunk], s_x1[kScChunk], s_y0[kScChunk], s_y1[kScChunk], s_lvl[kScChunk];
+    __shared__ uint8_t s_st[kScChunk];
+    const int k = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int64_t first = (int64_t)blockIdx.x * kScChunk;
+    const double* K = kf.f64 + (int64_t)k * kScKfF64;
+    const int cols = kf.i32[3 * k], rows = kf.i32[3 * k + 1], levels = kf.i32[3 * k + 2];
+    const double* scale = kf.scale + kf.lvl_off[k];
+    // ---- phase 1: one point per thread
+    {
+        int lvl = -1, x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+        unsigned st = 0;
+        double u = 0.0, v = 0.0, Eu = 0.0, Ev = 0.0, r = 0.0;
+        const int64_t i = first + tid;
+        if (i < pt.n) {
+            const double* P = pt.f64 + i * kScPtF64;
+            const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];  // K[4], bf, is not read
+            const double minX = K[20], maxX = K[21], minY = K[22], maxY = K[23], winv = K[24], hinv = K[25],
+                         lsf = K[26];
+            const double p0 = P[0], p1 = P[1], p2 = P[2];
+            const double xc = ((K[5] * p0 + K[6] * p1) + K[7] * p2) + K[14];
+            const double yc = ((K[8] * p0 + K[9] * p1) + K[10] * p2) + K[15];
+            const double zc = ((K[11] * p0 + K[12] * p1) + K[13] * p2) + K[16];
+            const double Ex = 4.0 * eps * (((fabs(K[5] * p0) + fabs(K[6] * p1)) + fabs(K[7] * p2)) + fabs(K[14]));
+            const double Ey = 4.0 * eps * (((fabs(K[8] * p0) + fabs(K[9] * p1)) + fabs(K[10] * p2)) + fabs(K[15]));
+            const double Ez = 4.0 * eps * (((fabs(K[11] * p0) + fabs(K[12] * p1)) + fabs(K[13] * p2)) + fabs(K[16]));
+            do {
+                if (zc < 0.0) {
+                    if (-zc < Ez) st = ORBFE_FUSE_MARGINAL;
+                    break;
+                }
+                // zc == 0: fuse_kf_scw_mp runs on, 1 / 0 is inf, u and v end as inf or NaN and fail the image test
+                // below; the ckf search leaves at its z <= 0.  Neither reaches a window.
+                const double iz = 1.0 / zc;
+                const double xn = xc * iz, yn = yc * iz;
+                const double fxx = fx * xn, fyy = fy * yn;
+                u = fxx + cx;
+                v = fyy + cy;
+                const bool in = minX <= u && u < maxX && minY <= v && v < maxY;
+                if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
+                if (zc == 0.0) break;
+                const double rz = Ez / zc;
+                if (!(rz <= 0.25)) st = ORBFE_FUSE_MARGINAL;
+                const double Eiz = iz * (2.0 * rz + 2.0 * eps);
+                const double Ax = fabs(xc) * Eiz + Ex * (iz + Eiz), Ay = fabs(yc) * Eiz + Ey * (iz + Eiz);
+                const double Exn = Ax + eps * (fabs(xn) + Ax), Eyn = Ay + eps * (fabs(yn) + Ay);
+                const double Mu = fabs(fxx) + fabs(cx), Mv = fabs(fyy) + fabs(cy);
+                Eu = fabs(fx) * Exn + 4.0 * eps * Mu;
+                Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
+                if (!isfinite(((u + v) + Eu) + Ev)) {
+                    st = ORBFE_FUSE_MARGINAL;
+                    break;
+                }
+                if (fabs(u - minX) < Eu + eps * fabs(minX) || fabs(u - maxX) < Eu + eps * fabs(maxX) ||
+                    fabs(v - minY) < Ev + eps * fabs(minY) || fabs(v - maxY) < Ev + eps * fabs(maxY))
+                    st = ORBFE_FUSE_MARGINAL;
+                if (!in) break;
+                const double po0 = p0 - K[17], po1 = p1 - K[18], po2 = p2 - K[19];
+                const double dist = sqrt((po0 * po0 + po1 * po1) + po2 * po2);
+                const double Ed = 6.0 * eps * dist;
+                const double minD = P[6], maxD = P[7];
+                if (!isfinite(dist)) {
+                    st = ORBFE_FUSE_MARGINAL;
+                    break;
+                }
+                if (fabs(dist - minD) < Ed + eps * fabs(minD) || fabs(dist - maxD) < Ed + eps * fabs(maxD))
+                    st = ORBFE_FUSE_MARGINAL;
+                if (dist < minD || dist > maxD) break;
+                const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
+                const double dot = (t0 + t1) + t2;
+                const double half = 0.5 * dist;
+                if (fabs(dot - half) < 5.0 * eps * ((fabs(t0) + fabs(t1)) + fabs(t2)) + Ed) st = ORBFE_FUSE_MARGINAL;
+                if (dot < half) break;
+                const double q = log(P[8] / dist) / lsf;
+                if (!isfinite(q)) {
+                    st = ORBFE_FUSE_MARGINAL;
+                    break;
+                }
+                if (sc_near_int(q, 10.0 * eps / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
+                const double cq = ceil(q);
+                const int level = cq < 0.0 ? 0 : (cq > (double)(levels - 1) ? levels - 1 : (int)cq);
+                r = th * scale[level];
+                const double ax = ((u - minX) - r) * winv, bx = ((u - minX) + r) * winv;
+                const double ay = ((v - minY) - r) * hinv, by = ((v - minY) + r) * hinv;
+                if (!isfinite((ax + bx) + (ay + by))) {
+                    st = ORBFE_FUSE_MARGINAL;
+                    break;
+                }
+                const double Ewx = fabs(winv) * (Eu + 4.0 * eps * ((fabs(u) + fabs(minX)) + fabs(r)));
+                const double Ewy = fabs(hinv) * (Ev + 4.0 * eps * ((fabs(v) + fabs(minY)) + fabs(r)));
+                if (sc_near_int(ax, Ewx) || sc_near_int(bx, Ewx) || sc_near_int(ay, Ewy) || sc_near_int(by, Ewy))
+                    st = ORBFE_FUSE_MARGINAL;
+                const double fax = floor(ax), cbx = ceil(bx), fay = floor(ay), cby = ceil(by);
+                // the four early returns of get_features_in_area
+                if (fax >= (double)cols || cbx < 0.0 || fay >= (double)rows || cby < 0.0) break;
+                x0 = fax < 0.0 ? 0 : (int)fax;
+                x1 = cbx > (double)(cols - 1) ? cols - 1 : (int)cbx;
+                y0 = fay < 0.0 ? 0 : (int)fay;
+                y1 = cby > (double)(rows - 1) ? rows - 1 : (int)cby;
+                lvl = level;
+            } while (false);
+        }
+        s_u[tid] = u;
+        s_v[tid] = v;
+        s_eu[tid] = Eu;
+        s_ev[tid] = Ev;
+        s_r[tid] = r;
+        s_x0[tid] = (int16_t)x0;
+        s_x1[tid] = (int16_t)x1;
+        s_y0[tid] = (int16_t)y0;
+        s_y1[tid] = (int16_t)y1;
+        s_lvl[tid] = (int16_t)lvl;
+        s_st[tid] = (uint8_t)st;
+    }
+    __syncthreads();
+    // ---- phase 2: kScGroup lanes per point
+    const int g = tid / kScGroup, l = tid % kScGroup;
+    const int64_t base = kf.off[k];
+    const double* xy = kf.xy + 2 * base;
+    const int32_t* oct = kf.octave + base;
+    const uint8_t* blk = kf.blocked ? kf.blocked + base : nullptr;
+    const uint4* desc = reinterpret_cast<const uint4*>(kf.desc + base * 32);
+    const int32_t* coff = kf.cell_off + kf.cell_at[k];
+    const int32_t* cidx = kf.cell_idx + kf.idx_at[k];
+    for (int j = g; j < kScChunk; j += kScChunk / kScGroup) {
+        const int64_t i = first + j;
+        if (i >= pt.n) break;
+        const int level = s_lvl[j];
+        unsigned st = s_st[j];
+        unsigned key = kScNone;
+        if (level >= 0) {
+            const double u = s_u[j], v = s_v[j], Eu = s_eu[j], Ev = s_ev[j], r = s_r[j];
+            const int x0 = s_x0[j], x1 = s_x1[j], y0 = s_y0[j], y1 = s_y1[j];
+            const uint4* pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
+            const uint4 qa = pd[0], qb = pd[1];
+            const double er_r = eps * fabs(r);
+            for (int ix = x0; ix <= x1; ++ix) {
+                const int a = coff[ix * rows + y0], b = coff[ix * rows + y1 + 1];
+                for (int pos = a + l; pos < b; pos += kScGroup) {
+                    const int f = cidx[pos];
+                    if (blk && blk[f]) continue;
+                    const double kx = xy[2 * f], ky = xy[2 * f + 1];
+                    const double dx = kx - u, dy = ky - v;
+                    const double Edx = Eu + 2.0 * eps * (fabs(kx) + fabs(u)), Edy = Ev + 2.0 * eps * (fabs(ky) + fabs(v));
+                    if (fabs(fabs(dx) - r) < Edx + er_r || fabs(fabs(dy) - r) < Edy + er_r) st = ORBFE_FUSE_MARGINAL;
+                    if (!(fabs(dx) < r && fabs(dy) < r)) continue;
+                    const int o = oct[f];
+                    if (o < level - 1 || o > level) continue;
+                    const uint4 da = desc[2 * f], db = desc[2 * f + 1];
+                    const unsigned d = __popc(da.x ^ qa.x) + __popc(da.y ^ qa.y) + __popc(da.z ^ qa.z) +
+                                       __popc(da.w ^ qa.w) + __popc(db.x ^ qb.x) + __popc(db.y ^ qb.y) +
+                                       __popc(db.z ^ qb.z) + __popc(db.w ^ qb.w);
+                    key = min(key, (d << 16) | (unsigned)pos);
+                }
+            }
+#pragma unroll
+            for (int o = kScGroup / 2; o; o >>= 1) {
+                key = min(key, (unsigned)__shfl_xor((int)key, o, kScGroup));
+                st |= (unsigned)__shfl_xor((int)st, o, kScGroup);
+            }
+        }
+        if (l == 0) {
+            const int64_t at = (int64_t)k * out.stride + i;
+            out.best_idx[at] = key == kScNone ? -1 : cidx[key & 0xFFFFu];
+            out.best_dist[at] = key == kScNone ? -1 : (int)(key >> 16);
+            out.status[at] = (uint8_t)st;
+        }
+    }
+}
+
+}  // namespace orbfe
+
+namespace {
+
+// scratch of orbfe_scw_search: process-wide, created on first use and never torn down (the HIP runtime may
+// already be gone when static destructors run); callers on several threads take turns
+struct ScwSearcher {
+    std::mutex mu;
+    DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, blocked bytes, status
+    DevBuf<double> d_f64;   // keyframe scalars, xy, scale, point scalars
+    DevBuf<int64_t> d_i64;  // off, cell_at, idx_at, lvl_off
+    DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, best_idx, best_dist
+    std::vector<int32_t> h_i32;
+    std::vector<uint8_t> h_st;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float last_ms = 0.f;
+};
+ScwSearcher& searcher() {
+    static ScwSearcher* m = new ScwSearcher;
+    return *m;
+}
+
+std::string at_kf(int32_t k, const std::string& what) { return "keyframe " + std::to_string(k) + ": " + what; }
+
+bool all_finite(const double* v, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                     const int32_t* octave, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+                     const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                     const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                     double th, double eps, const orbfe_scw_out* out, int64_t out_stride) {
+    return guarded([&] {
+        if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
+        if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
+        if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
+            throw Error(ORBFE_EINVAL, "th and eps must be finite and eps not negative");
+        if (n_kf == 0 || n_pts == 0) return;
+        if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale || !pt_f64 ||
+            !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
+            throw Error(ORBFE_EINVAL, "null argument");
+        if (out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
+        if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
+            throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
+        for (int32_t k = 0; k < n_kf; ++k)
+            if (off[k + 1] < off[k] || cell_at[k + 1] < cell_at[k] || idx_at[k + 1] < idx_at[k] ||
+                lvl_off[k + 1] < lvl_off[k])
+                throw Error(ORBFE_EINVAL, at_kf(k, "offsets must not decrease"));
+        for (int32_t k = 0; k < n_kf; ++k) {
+            const int64_t n = off[k + 1] - off[k], nc = cell_at[k + 1] - cell_at[k], ni = idx_at[k + 1] - idx_at[k],
+                          nl = lvl_off[k + 1] - lvl_off[k];
+            if (n > ORBFE_BOW_MAX_FRAME || ni > ORBFE_BOW_MAX_FRAME)
+                throw Error(ORBFE_EINVAL, at_kf(k, "more features or grid entries than the limit of " +
+                                                       std::to_string(ORBFE_BOW_MAX_FRAME) + " per keyframe"));
+            // slot 4 (bf in orbfe_fuse_search's block) is not read and may hold anything
+            const double* Kk = kf_f64 + (int64_t)k * ORBFE_FUSE_KF_F64;
+            if (!(all_finite(Kk, 4) && all_finite(Kk + 5, ORBFE_FUSE_KF_F64 - 5)))
+                throw Error(ORBFE_EINVAL, at_kf(k, "a scalar is not finite"));
+            const int64_t cols = kf_i32[3 * k], rows = kf_i32[3 * k + 1], levels = kf_i32[3 * k + 2];
+            if (levels <= 0) throw Error(ORBFE_EINVAL, at_kf(k, "the level count must be positive"));
+            if (nl != levels) throw Error(ORBFE_EINVAL, at_kf(k, "the level table does not have one entry per level"));
+            if (cols <= 0 || rows <= 0 || cols > 4096 || rows > 4096)
+                throw Error(ORBFE_EINVAL, at_kf(k, "grid columns and rows must lie in [1, 4096]"));
+            if (nc != cols * rows + 1)
+                throw Error(ORBFE_EINVAL, at_kf(k, "the grid needs columns * rows + 1 cell offsets"));
+            if (!all_finite(scale + lvl_off[k], nl))
+                throw Error(ORBFE_EINVAL, at_kf(k, "a level table entry is not finite"));
+            if (n > 0 && (!xy || !octave || !desc32)) throw Error(ORBFE_EINVAL, "null argument");
+            if (n > 0 && !all_finite(xy + 2 * off[k], 2 * n))
+                throw Error(ORBFE_EINVAL, at_kf(k, "a keypoint coordinate is not finite"));
+            for (int64_t i = 0; i < n; ++i) {
+                const int32_t o = octave[off[k] + i];
+                if (o < 0 || o >= levels) throw Error(ORBFE_EINVAL, at_kf(k, "an octave is outside the level table"));
+            }
+            const int32_t* co = cell_off + cell_at[k];
+            if (co[0] != 0) throw Error(ORBFE_EINVAL, at_kf(k, "the first cell offset must be 0"));
+            for (int64_t c = 0; c < nc - 1; ++c)
+                if (co[c + 1] < co[c]) throw Error(ORBFE_EINVAL, at_kf(k, "cell offsets must not decrease"));
+            if (co[nc - 1] != ni) throw Error(ORBFE_EINVAL, at_kf(k, "the last cell offset is not the grid entry count"));
+            if (ni > 0 && !cell_idx) throw Error(ORBFE_EINVAL, "null argument");
+            for (int64_t e = 0; e < ni; ++e) {
+                const int32_t f = cell_idx[idx_at[k] + e];
+                if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
+            }
+        }
+        if (!all_finite(pt_f64, n_pts * ORBFE_FUSE_PT_F64)) throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+        const size_t nk = (size_t)n_kf, np = (size_t)n_pts, os = (size_t)out_stride;
+        const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
+                     nl = (size_t)lvl_off[n_kf];
+        const bool has_blocked = blocked != nullptr && n > 0;
+        ScwSearcher& m = searcher();
+        std::lock_guard<std::mutex> lk(m.mu);
+        if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+        for (hipEvent_t& e : m.ev)
+            if (!e) HIPCK(hipEventCreate(&e));
+        hipStream_t s = m.stream;
+        // descriptors are read as uint4: both blocks start on 16 bytes
+        m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + pad16(n) + nk * os);
+        m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + nl + np * ORBFE_FUSE_PT_F64);
+        m.d_i64.ensure(4 * (nk + 1));
+        m.d_i32.ensure(3 * nk + n + nc + ni + 2 * nk * os);
+        uint8_t* d_desc = m.d_u8.p;
+        uint8_t* d_pdesc = d_desc + pad16(n * 32);
+        uint8_t* d_blk = d_pdesc + pad16(np * 32);
+        uint8_t* d_st = d_blk + pad16(n);
+        double* d_kf = m.d_f64.p;
+        double* d_xy = d_kf + nk * ORBFE_FUSE_KF_F64;
+        double* d_scale = d_xy + 2 * n;
+        double* d_pt = d_scale + nl;
+        int64_t* d_off = m.d_i64.p;
+        int64_t* d_cat = d_off + nk + 1;
+        int64_t* d_iat = d_cat + nk + 1;
+        int64_t* d_lvl = d_iat + nk + 1;
+        int32_t* d_ki = m.d_i32.p;
+        int32_t* d_oct = d_ki + 3 * nk;
+        int32_t* d_coff = d_oct + n;
+        int32_t* d_cidx = d_coff + nc;
+        int32_t* d_bi = d_cidx + ni;
+        int32_t* d_bd = d_bi + nk * os;
+        auto up = [&](void* dst, const void* src, size_t bytes) {
+            if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+        };
+        up(d_desc, desc32, n * 32);
+        up(d_pdesc, pt_desc32, np * 32);
+        if (has_blocked) up(d_blk, blocked, n);
+        up(d_kf, kf_f64, nk * ORBFE_FUSE_KF_F64 * sizeof(double));
+        up(d_xy, xy, 2 * n * sizeof(double));
+        up(d_scale, scale, nl * sizeof(double));
+        up(d_pt, pt_f64, np * ORBFE_FUSE_PT_F64 * sizeof(double));
+        up(d_off, off, (nk + 1) * sizeof(int64_t));
+        up(d_cat, cell_at, (nk + 1) * sizeof(int64_t));
+        up(d_iat, idx_at, (nk + 1) * sizeof(int64_t));
+        up(d_lvl, lvl_off, (nk + 1) * sizeof(int64_t));
+        up(d_ki, kf_i32, 3 * nk * sizeof(int32_t));
+        up(d_oct, octave, n * sizeof(int32_t));
+        up(d_coff, cell_off, nc * sizeof(int32_t));
+        up(d_cidx, cell_idx, ni * sizeof(int32_t));
+        ScKfs kf{};
+        kf.f64 = d_kf;
+        kf.i32 = d_ki;
+        kf.off = d_off;
+        kf.cell_at = d_cat;
+        kf.idx_at = d_iat;
+        kf.lvl_off = d_lvl;
+        kf.xy = d_xy;
+        kf.scale = d_scale;
+        kf.octave = d_oct;
+        kf.cell_off = d_coff;
+        kf.cell_idx = d_cidx;
+        kf.desc = d_desc;
+        kf.blocked = has_blocked ? d_blk : nullptr;
+        const ScPts pt{d_pt, d_pdesc, n_pts};
+        const ScOut d{d_bi, d_bd, d_st, out_stride};
+        const unsigned chunks = (unsigned)((np + kScChunk - 1) / kScChunk);
+        HIPCK(hipEventRecord(m.ev[0], s));
+        hipLaunchKernelGGL(k_scw_search, dim3(chunks, (unsigned)n_kf), dim3(kScChunk), 0, s, kf, pt, th, eps, d);
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(m.ev[1], s));
+        // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
+        // the caller's arrays
+        m.h_i32.resize(2 * nk * os);
+        m.h_st.resize(nk * os);
+        HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * nk * os * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, nk * os, hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+        for (size_t k = 0; k < nk; ++k) {
+            std::memcpy(out->best_idx + k * os, &m.h_i32[k * os], np * sizeof(int32_t));
+            std::memcpy(out->best_dist + k * os, &m.h_i32[nk * os + k * os], np * sizeof(int32_t));
+            std::memcpy(out->status + k * os, &m.h_st[k * os], np);
+        }
+    });
+}
+
+int orbfe_scw_search_last_ms(float* ms) {
+    return guarded([&] {
+        if (!ms) throw Error(ORBFE_EINVAL, "null argument");
+        ScwSearcher& m = searcher();
+        std::lock_guard<std::mutex> lk(m.mu);
+        *ms = m.last_ms;
+    });
+}
+
+}  // extern "C"

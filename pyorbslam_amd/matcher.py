@@ -32,6 +32,7 @@ search_for_triangulation_many (k_tri_match).  Each returns what the loop of sing
 the kernels' arrays cannot express, or whose float64 decision lies within rounding of its threshold, takes the
 single search.  fuse_pkf_mp_many (k_fuse_search) does the same for LocalMapping's fusion loops: one launch for
 the search of every (keyframe, point), then the matches applied on the host in the reference's order.
+fuse_kf_scw_mp_many and search_by_projection_ckf_scw_mp (k_scw_search) do it for LoopClosing's two Sim3 searches.
 """
 from __future__ import annotations
 
@@ -644,6 +645,47 @@ def fuse_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, cell_at, 
     call("orbfe_fuse_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(u_right), ptr(desc),
          ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), ptr(inv_sigma2), n_kf,
          ptr(pt_f64), ptr(pt_desc), n_pts, float(th), float(eps), C.byref(out), n_pts)
+    return dict(best_idx=bi, best_dist=bd, status=st)
+
+
+def scw_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                      scale, pt_f64, pt_desc, th, eps) -> dict:
+    """orbfe_scw_search (k_scw_search, include/orbfe.h): the search half of ORBMatcher.fuse_kf_scw_mp
+    (ORBMatcher.py:409-468) and of search_by_projection_ckf_scw_mp (:863-916) for every (keyframe, point) in one
+    launch.  The arrays are fuse_search_arrays' without u_right and inv_sigma2; the pose slots of kf_f64 hold what
+    the Sim3 gives and its bf slot is not read.  blocked: None, or one byte per feature (concatenated at `off`),
+    non-zero for a feature that is no candidate.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
+    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
+    kf_i32 = np.ascontiguousarray(kf_i32, np.int32).reshape(-1, 3)
+    pt_f64 = np.ascontiguousarray(pt_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
+    pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
+    off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
+    xy, scale = arr(xy, np.float64), arr(scale, np.float64)
+    octave, cell_off, cell_idx = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32)
+    desc, blocked = arr(desc, np.uint8), arr(blocked, np.uint8)
+    n_kf, n_pts = len(kf_f64), len(pt_f64)
+    if len(kf_i32) != n_kf or len(pt_desc) != n_pts:
+        raise ValueError("kf_i32 / pt_desc do not cover the keyframes / points")
+    for a in (off, cell_at, idx_at, lvl_off):
+        if a is None or len(a) != n_kf + 1:
+            raise ValueError("an offset array does not have one entry per keyframe and one more")
+    if n_kf:
+        n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
+        for a, need in ((xy, 2 * n), (octave, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni), (scale, nl)):
+            if need > 0 and (a is None or a.size < need):
+                raise ValueError("a per-keyframe array is shorter than its offsets say")
+        if blocked is not None and blocked.size < n:
+            raise ValueError("blocked does not have one byte per feature")
+    bi = np.full((n_kf, n_pts), -1, np.int32)
+    bd = np.full((n_kf, n_pts), -1, np.int32)
+    st = np.zeros((n_kf, n_pts), np.uint8)
+    out = _lib.ScwOut(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
+    call("orbfe_scw_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(desc), ptr(blocked),
+         ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), n_kf, ptr(pt_f64),
+         ptr(pt_desc), n_pts, float(th), float(eps), C.byref(out), n_pts)
     return dict(best_idx=bi, best_dist=bd, status=st)
 
 
@@ -1475,6 +1517,185 @@ class ORBMatcher:
                 n_fused += 1
         return n_fused, vpReplacePoint
 
+    def _scw_one(self, pKF, pMP, Rcw, tcw, Ow, th, vpMatched=None):
+        """(best_dist, best_idx) of one point in one keyframe with the reference's own expressions on the objects:
+        ORBMatcher.py:415-468 (fuse_kf_scw_mp) when vpMatched is None, :867-916 (search_by_projection_ckf_scw_mp)
+        against that vpMatched otherwise; the few distances are host popcounts.  best_idx is -1 without a
+        candidate."""
+        ckf = vpMatched is not None
+        best_dist, best_idx = (256 if ckf else float('inf')), -1
+        pr = self._project_checked(pMP, pKF, Rcw, tcw, ckf)
+        if pr is None:
+            return best_dist, best_idx
+        u, v, _, p3Dw = pr
+        if not pKF.is_in_image(u, v):
+            return best_dist, best_idx
+        lvl = self._distance_gates(pMP, pKF, p3Dw, Ow)
+        if lvl is None:
+            return best_dist, best_idx
+        vIndices = pKF.get_features_in_area(u, v, th * pKF.mvScaleFactors[lvl])
+        if not vIndices:
+            return best_dist, best_idx
+        d = pMP.get_descriptor()
+        for idx in vIndices:
+            if ckf and vpMatched[idx] is not None:
+                continue
+            if not lvl - 1 <= pKF.mvKeysUn[idx].octave <= lvl:
+                continue
+            dist = descriptor_distance(d, pKF.mDescriptors[idx])
+            if dist < best_dist:
+                best_dist = dist
+                best_idx = idx
+        return best_dist, best_idx
+
+    @staticmethod
+    def _scw_frame(pKF, Scw, pose):
+        """(_FuseFrame of pKF with the pose slots filled from Scw, (Rcw, tcw, Ow) as pose(Scw) gave them), or None
+        when _fuse_frame refuses the keyframe, when Scw is not a finite 4 x 4 float32 / float64 array with a non-zero
+        first row, or when the pose it gives is not finite.  f.f32 tells whether Scw is float32."""
+        if not (type(Scw) is np.ndarray and Scw.shape == (4, 4) and Scw.dtype in _POSE_DT
+                and bool(np.isfinite(Scw).all()) and bool(Scw[0, :3].any())):
+            return None
+        f = _fuse_frame(pKF)
+        if f is None:
+            return None
+        with np.errstate(all="ignore"):
+            Rcw, tcw, Ow = pose(Scw)
+        R, t, O = _pose_part(Rcw, (3, 3)), _pose_part(tcw, (3, 1)), _pose_part(Ow, (3, 1))
+        if R is None or t is None or O is None:
+            return None
+        f.f64 = f.f64.copy()
+        f.f64[5:20] = R[0] + t[0] + O[0]
+        f.f32 = Scw.dtype == _F32_DT
+        return f, (Rcw, tcw, Ow)
+
+    @staticmethod
+    def _scw_points(vpPoints, skip):
+        """The points once: (slot per list position, rows, descriptor rows, any float32).  slot >= 0 is the row sent
+        to the device, -1 not expressible (_fuse_point), -2 skipped by skip(pMP)."""
+        slot, rows, descs, f32 = [], [], [], False
+        for pMP in vpPoints:
+            if skip(pMP):
+                slot.append(-2)
+                continue
+            pt = _fuse_point(pMP)
+            if pt is None:
+                slot.append(-1)
+                continue
+            slot.append(len(rows))
+            rows.append(pt[0])
+            descs.append(pt[1])
+            f32 = f32 or pt[2]
+        return slot, rows, descs, f32
+
+    @staticmethod
+    def _scw_launch(fr, blocked, rows, descs, th, f32):
+        def offs(lens):
+            o = np.zeros(len(fr) + 1, np.int64)
+            np.cumsum(lens, out=o[1:])
+            return o
+        cat = lambda name: np.concatenate([getattr(f, name) for f in fr])  # noqa: E731
+        return scw_search_arrays(np.stack([f.f64 for f in fr]), np.stack([f.i32 for f in fr]),
+                                 offs([len(f.xy) for f in fr]), cat("xy"), cat("octave"), cat("desc"), blocked,
+                                 offs([len(f.cell_off) for f in fr]), cat("cell_off"),
+                                 offs([len(f.cell_idx) for f in fr]), cat("cell_idx"),
+                                 offs([len(f.scale) for f in fr]), cat("scale"), np.array(rows, np.float64),
+                                 np.stack(descs), th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+
+    def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
+        """What this loop returns (LoopClosing.search_and_fuse, LoopClosing.py:352-367, with after = its replace
+        loop), leaving every map point and keyframe as the loop leaves them, event for event, from one k_scw_search
+        launch for every (keyframe, point) of the call:
+
+            out = []
+            for kf, Scw in zip(kfs, Scws):
+                r = self.fuse_kf_scw_mp(kf, Scw, vpPoints, th, [None] * len(vpPoints))
+                if after is not None:
+                    after(kf, r[1])
+                out.append(r)
+
+        Per keyframe Rcw, tcw and Ow come from _sim3_to_pose(Scw), the reference's own expressions on the host.  The
+        points are read once: every point that is not bad and that the arrays can express (_fuse_point).  The replay
+        runs keyframe by keyframe; at a keyframe's turn spAlreadyFound = kf.get_map_points() is the snapshot of that
+        moment, as the reference's is, and then point by point in list order with is_bad() read at that moment.
+        ORBMatcher.py:470-478 is applied to the device's best candidate, get_map_point(best_idx) read at that moment,
+        so a point added earlier in the same pass is seen.  One item is redone alone with the reference's
+        expressions (_scw_one) when it came back ORBFE_FUSE_MARGINAL, when its point is not expressible, or when
+        its point's descriptor is no longer the bytes that were sent (MapPoint.replace recomputes the survivor's).
+        A keyframe _fuse_frame refuses takes fuse_kf_scw_mp whole at its place in the order, as does one whose Scw
+        is not a finite 4 x 4 float32 / float64 array with a non-zero first row, and every keyframe when th is not a
+        plain finite number.
+
+        after(kf, vpReplacePoint) runs after each keyframe.  It may replace points, add observations and make
+        points bad, which is what search_and_fuse does; it must not move points or change the level tables or grids
+        of keyframes still to come, which were read before the first keyframe's turn."""
+        kfs, Scws = list(kfs), list(Scws)
+        if len(kfs) != len(Scws):
+            raise ValueError("one Scw per keyframe")
+        if not isinstance(vpPoints, (list, tuple)):
+            vpPoints = list(vpPoints)
+        n_pts = len(vpPoints)
+
+        def whole(kf, Scw):
+            r = self.fuse_kf_scw_mp(kf, Scw, vpPoints, th, [None] * n_pts)
+            if after is not None:
+                after(kf, r[1])
+            return r
+        if type(th) not in _TH_SET or not np.isfinite(th):
+            return [whole(kf, Scw) for kf, Scw in zip(kfs, Scws)]
+        frames = [self._scw_frame(kf, Scw, self._sim3_to_pose) for kf, Scw in zip(kfs, Scws)]
+        live = [k for k, f in enumerate(frames) if f is not None]
+        slot, rows, descs, f32 = self._scw_points(vpPoints, _IS_BAD) if live else ([], [], [], False)
+        res, snaps = None, []
+        if live and rows:
+            fr = [frames[k][0] for k in live]
+            snaps = [d.tobytes() for d in descs]
+            res = self._scw_launch(fr, None, rows, descs, th, f32 or any(f.f32 for f in fr))
+        slot_arr = np.array(slot, np.int64)
+        alone = np.flatnonzero(slot_arr == -1)   # list positions whose point goes alone in every keyframe
+        sent = np.flatnonzero(slot_arr >= 0)     # list positions in device row order
+        row = {k: j for j, k in enumerate(live)}
+        out = []
+        for k, (kf, Scw) in enumerate(zip(kfs, Scws)):
+            if frames[k] is None:
+                out.append(whole(kf, Scw))
+                continue
+            Rcw, tcw, Ow = frames[k][1]
+            if res is None:
+                todo, bi, bd, st = alone, None, None, None
+            else:
+                j = row[k]
+                bi, bd, st = res["best_idx"][j], res["best_dist"][j], res["status"][j]
+                # an item without a candidate and without a marginal decision does nothing, whatever its
+                # descriptor has become; the others in list order
+                todo = np.sort(np.concatenate([alone, sent[(bi >= 0) | (st != 0)]]))
+                bi, bd, st = bi.tolist(), bd.tolist(), st.tolist()
+            spAlreadyFound = kf.get_map_points()
+            rep = [None] * n_pts
+            n_fused = 0
+            for i in todo.tolist():
+                pMP = vpPoints[i]
+                if pMP.is_bad() or pMP in spAlreadyFound:
+                    continue
+                s = slot[i]
+                if s >= 0 and not st[s] and pMP.get_descriptor().tobytes() == snaps[s]:
+                    best_dist, best_idx = bd[s], bi[s]
+                else:
+                    best_dist, best_idx = self._scw_one(kf, pMP, Rcw, tcw, Ow, th)
+                if best_idx >= 0 and best_dist <= TH_LOW:
+                    pMPinKF = kf.get_map_point(best_idx)
+                    if pMPinKF:
+                        if not pMPinKF.is_bad():
+                            rep[i] = pMPinKF
+                    else:
+                        pMP.add_observation(kf, best_idx)
+                        kf.add_map_point(pMP, best_idx)
+                    n_fused += 1
+            if after is not None:
+                after(kf, rep)
+            out.append((n_fused, rep))
+        return out
+
     def _fuse_cands(self, pKF, pMP, th, K):
         """The search of fuse_pkf_mp for one point, up to the descriptor distances (ORBMatcher.py:498-560): the
         candidates that pass the octave filter and the chi-square, in visiting order, or None when the point is
@@ -1909,8 +2130,66 @@ class ORBMatcher:
                 n_found += 1
         return n_found, vpMatches12
 
+    @staticmethod
+    def _ckf_pose(Scw):
+        """ORBMatcher.py:853-857."""
+        sRcw = Scw[:3, :3]
+        scw = np.linalg.norm(sRcw[0])
+        Rcw = sRcw / scw
+        tcw = Scw[:3, 3:4] / scw
+        return Rcw, tcw, -Rcw.T @ tcw
+
     # ORBMatcher.py:850-922
     def search_by_projection_ckf_scw_mp(self, pKF, Scw, vpPoints, vpMatched, th):
+        """LoopClosing.compute_sim3's search (LoopClosing.py:234) from one k_scw_search launch: the prefilter in list
+        order (pMP.is_bad() or pMP in spAlreadyFound, with spAlreadyFound = set(vpMatched) - {None} taken once),
+        blocked[idx] = vpMatched[idx] is not None taken once, then the replay in list order.  An item that came back
+        ORBFE_FUSE_MARGINAL, or whose point the arrays cannot express, or whose best candidate an earlier point of
+        this call has taken meanwhile, is redone alone against the current vpMatched (_scw_one); otherwise the
+        device's candidate is assigned when best_dist <= TH_LOW.  Taking candidates away never changes which of the
+        remaining ones is best, so the device's answer stands whenever its candidate is still free.  The host body
+        (_ckf_host) runs instead when _fuse_frame refuses the keyframe, when Scw is not a finite 4 x 4 float32 /
+        float64 array with a non-zero first row, when th is not a plain finite number, or when vpMatched is not a
+        list with one entry per feature.  It also runs where the HIP runtime sees no device: its only device work is
+        _batched, the seam the host-logic tests replace, so those tests keep reading the host body."""
+        sf = None
+        if type(th) in _TH_SET and np.isfinite(th) and isinstance(vpMatched, list) and _lib.device_present():
+            sf = self._scw_frame(pKF, Scw, self._ckf_pose)
+            if sf is not None and len(vpMatched) != len(sf[0].xy):
+                sf = None
+        if sf is None:
+            return self._ckf_host(pKF, Scw, vpPoints, vpMatched, th)
+        f, (Rcw, tcw, Ow) = sf
+        if not isinstance(vpPoints, (list, tuple)):
+            vpPoints = list(vpPoints)
+        spAlreadyFound = set(vpMatched) - {None}
+        blocked = np.fromiter((m is not None for m in vpMatched), np.uint8, count=len(vpMatched))
+        slot, rows, descs, f32 = self._scw_points(vpPoints, lambda p: p.is_bad() or p in spAlreadyFound)
+        slot_arr = np.array(slot, np.int64)
+        todo = np.flatnonzero(slot_arr == -1)
+        if rows:
+            res = self._scw_launch([f], blocked, rows, descs, th, f32 or f.f32)
+            bi, bd, st = res["best_idx"][0], res["best_dist"][0], res["status"][0]
+            # what is left of a point's candidates is never closer than its best: above TH_LOW nothing is assigned
+            sent = np.flatnonzero(slot_arr >= 0)
+            todo = np.sort(np.concatenate([todo, sent[(st != 0) | ((bi >= 0) & (bd <= TH_LOW))]]))
+            bi, bd, st = bi.tolist(), bd.tolist(), st.tolist()
+        n_matches = 0
+        for i in todo.tolist():
+            pMP = vpPoints[i]
+            s = slot[i]
+            if s >= 0 and not st[s] and vpMatched[bi[s]] is None:
+                best_dist, best_idx = bd[s], bi[s]
+            else:
+                best_dist, best_idx = self._scw_one(pKF, pMP, Rcw, tcw, Ow, th, vpMatched)
+            if best_idx >= 0 and best_dist <= TH_LOW:
+                vpMatched[best_idx] = pMP
+                n_matches += 1
+        return n_matches, vpMatched
+
+    def _ckf_host(self, pKF, Scw, vpPoints, vpMatched, th):
+        """search_by_projection_ckf_scw_mp on the host, point by point (only the Hamming distances run on the
+        device): the fallback of the public method."""
         sRcw = Scw[:3, :3]
         scw = np.linalg.norm(sRcw[0])
         Rcw = sRcw / scw
