@@ -1,19 +1,34 @@
-// orbfe_fuse.hip — the search half of ORBMatcher.fuse_pkf_mp (ORBMatcher.py:498-567) for every (keyframe, map
-// point) of a call in one launch on gfx950.
+// orbfe_fuse.hip — the search half of the reference's three projection searches, for every (keyframe, map point) of a
+// call in one launch on gfx950: ORBMatcher.fuse_pkf_mp (ORBMatcher.py:498-567) as k_fuse_search, and LoopClosing's two
+// Sim3 searches, ORBMatcher.fuse_kf_scw_mp (:395-480) and ORBMatcher.search_by_projection_ckf_scw_mp (:850-922), as
+// k_scw_search.  Both kernels are instantiations of one body, proj_search<kScw>.
 //
 // The reference projects each map point into a keyframe, gates it (depth sign, image bounds, scale-invariance
 // distances, viewing angle), predicts its pyramid level, searches the keyframe's grid in a window of radius
-// th * scale[level] (KeyFrame.get_features_in_area, KeyFrame.py:432-460), filters the candidates by octave and by a
-// chi-square on the reprojection error, and keeps the candidate of the smallest Hamming distance; among equal
-// distances the EARLIEST in visiting order (column ix outer, row iy inner, the cell's list as stored) wins, because
-// it replaces only on dist < bestDist.  None of this reads what a fusion changes, so it runs here for all items at
-// once and the caller applies the matches afterwards in the reference's order.
+// th * scale[level] (KeyFrame.get_features_in_area, KeyFrame.py:432-460), keeps the candidates whose octave is the
+// level or one below, and takes the candidate of the smallest Hamming distance; among equal distances the EARLIEST
+// in visiting order (column ix outer, row iy inner, the cell's list as stored) wins, because it replaces only on
+// dist < bestDist.  None of this reads what a fusion changes, so it runs here for all items at once and the caller
+// applies the matches afterwards in the reference's order.
 //
-// k_fuse_search: a workgroup is (keyframe, chunk of kFuChunk points).  Phase 1: thread t does point t's geometry in
-// IEEE double (-ffp-contract=off, correctly rounded division and square root) and leaves u, v, ur, their error
-// bounds, the radius, the level and the clamped cell window in LDS.  Phase 2: groups of kFuGroup lanes take the
+// What the two variants do not share:
+//   k_fuse_search  also projects the right coordinate ur = u - bf / z and filters the candidates by a chi-square on
+//                  the reprojection error (three terms against 7.8 for a stereo feature, two against 5.99 for a mono
+//                  one).
+//   k_scw_search   has neither (slot 4 of the keyframe block, bf, is not read; u_right and inv_sigma2 are null); the
+//                  pose is the one a Sim3 gives (the caller divides the scale out on the host, with the reference's
+//                  expressions); and it has one more input: a byte per feature that takes the feature out of the
+//                  candidates (the ckf search skips a feature whose vpMatched slot is taken).  A blocked entry is
+//                  skipped first: it decides nothing, so it marks nothing either.
+//
+// The depth gate: fuse_pkf_mp and fuse_kf_scw_mp skip z < 0, the ckf search z <= 0.  At z == 0 the first two run on to
+// 1 / 0, u and v become inf or NaN and fail the image test, so all three skip the point and one code path serves them.
+//
+// proj_search: a workgroup is (keyframe, chunk of kPsChunk points).  Phase 1: thread t does point t's geometry in
+// IEEE double (-ffp-contract=off, correctly rounded division and square root) and leaves u, v (and ur), their error
+// bounds, the radius, the level and the clamped cell window in LDS.  Phase 2: groups of kPsGroup lanes take the
 // chunk's points in turn; for one column ix the window's cells are one contiguous range of the grid's CSR, whose
-// entries the lanes take kFuGroup at a time.  A lane's key is dist << 16 | position in the keyframe's CSR (all ones
+// entries the lanes take kPsGroup at a time.  A lane's key is dist << 16 | position in the keyframe's CSR (all ones
 // without a candidate); the __shfl_xor minimum over the group is the smallest distance and among equals the
 // earliest visited.
 //
@@ -40,28 +55,30 @@ using namespace orbfe;
 
 namespace orbfe {
 
-constexpr int kFuChunk = ORBFE_FUSE_CHUNK;  // points per workgroup, one thread each in phase 1
-constexpr int kFuGroup = 16;                // lanes that share one point's candidates in phase 2
-constexpr unsigned kFuNone = 0xFFFFFFFFu;
-constexpr int kFuKfF64 = ORBFE_FUSE_KF_F64;
-constexpr int kFuPtF64 = ORBFE_FUSE_PT_F64;
+constexpr int kPsChunk = ORBFE_FUSE_CHUNK;  // points per workgroup, one thread each in phase 1
+constexpr int kPsGroup = 16;                // lanes that share one point's candidates in phase 2
+constexpr unsigned kPsNone = 0xFFFFFFFFu;
+constexpr int kPsKfF64 = ORBFE_FUSE_KF_F64;
+constexpr int kPsPtF64 = ORBFE_FUSE_PT_F64;
 
-struct FuKfs {
-    const double* f64;   // kFuKfF64 per keyframe
+struct PsKfs {
+    const double* f64;   // kPsKfF64 per keyframe
     const int32_t* i32;  // cols, rows, levels per keyframe
     const int64_t *off, *cell_at, *idx_at, *lvl_off;
-    const double *xy, *u_right, *scale, *inv_sigma2;
+    const double *xy, *scale;
+    const double *u_right, *inv_sigma2;  // k_fuse_search only
     const int32_t *octave, *cell_off, *cell_idx;
     const uint8_t* desc;
+    const uint8_t* blocked;  // k_scw_search only, and there null when nothing is blocked
 };
 
-struct FuPts {
-    const double* f64;  // kFuPtF64 per point
+struct PsPts {
+    const double* f64;  // kPsPtF64 per point
     const uint8_t* desc;
     int64_t n;
 };
 
-struct FuOut {
+struct PsOut {
     int32_t *best_idx, *best_dist;
     uint8_t* status;
     int64_t stride;
@@ -69,28 +86,32 @@ struct FuOut {
 
 // every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
 // is this one exactly
-__device__ __forceinline__ bool fu_near_int(double a, double e) { return fabs(a - rint(a)) < e; }
+__device__ __forceinline__ bool near_int(double a, double e) { return fabs(a - rint(a)) < e; }
 
-__global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, double th, double eps, FuOut out) {
-    __shared__ double s_u[kFuChunk], s_v[kFuChunk], s_ur[kFuChunk], s_eu[kFuChunk], s_ev[kFuChunk], s_eur[kFuChunk],
-        s_r[kFuChunk];
-    __shared__ int16_t s_x0[kFuChunk], s_x1[kFuChunk], s_y0[kFuChunk], s_y1[kFuChunk], s_lvl[kFuChunk];
-    __shared__ uint8_t s_st[kFuChunk];
+template <bool kScw>
+__device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, double th, double eps,
+                                            const PsOut& out) {
+    __shared__ double s_u[kPsChunk], s_v[kPsChunk], s_eu[kPsChunk], s_ev[kPsChunk], s_r[kPsChunk];
+    __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, in k_fuse_search only
+    __shared__ int16_t s_x0[kPsChunk], s_x1[kPsChunk], s_y0[kPsChunk], s_y1[kPsChunk], s_lvl[kPsChunk];
+    __shared__ uint8_t s_st[kPsChunk];
     const int k = blockIdx.y;
     const int tid = threadIdx.x;
-    const int64_t first = (int64_t)blockIdx.x * kFuChunk;
-    const double* K = kf.f64 + (int64_t)k * kFuKfF64;
+    const int64_t first = (int64_t)blockIdx.x * kPsChunk;
+    const double* K = kf.f64 + (int64_t)k * kPsKfF64;
     const int cols = kf.i32[3 * k], rows = kf.i32[3 * k + 1], levels = kf.i32[3 * k + 2];
     const double* scale = kf.scale + kf.lvl_off[k];
     // ---- phase 1: one point per thread
     {
         int lvl = -1, x0 = 0, x1 = -1, y0 = 0, y1 = -1;
         unsigned st = 0;
-        double u = 0.0, v = 0.0, ur = 0.0, Eu = 0.0, Ev = 0.0, Eur = 0.0, r = 0.0;
+        double u = 0.0, v = 0.0, Eu = 0.0, Ev = 0.0, r = 0.0;
+        [[maybe_unused]] double ur = 0.0, Eur = 0.0;
         const int64_t i = first + tid;
         if (i < pt.n) {
-            const double* P = pt.f64 + i * kFuPtF64;
-            const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], bf = K[4];
+            const double* P = pt.f64 + i * kPsPtF64;
+            const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
+            [[maybe_unused]] const double bf = kScw ? 0.0 : K[4];  // k_scw_search does not read the slot
             const double minX = K[20], maxX = K[21], minY = K[22], maxY = K[23], winv = K[24], hinv = K[25],
                          lsf = K[26];
             const double p0 = P[0], p1 = P[1], p2 = P[2];
@@ -105,14 +126,18 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                     if (-zc < Ez) st = ORBFE_FUSE_MARGINAL;
                     break;
                 }
-                // zc == 0 runs on: 1 / 0 is inf, u and v end as inf or NaN and fail the image test below
+                // zc == 0 runs on: 1 / 0 is inf, u and v end as inf or NaN and fail the image test below (the ckf
+                // search leaves at its z <= 0; neither way reaches a window)
                 const double iz = 1.0 / zc;
                 const double xn = xc * iz, yn = yc * iz;
                 const double fxx = fx * xn, fyy = fy * yn;
                 u = fxx + cx;
                 v = fyy + cy;
-                const double bz = bf * iz;
-                ur = u - bz;
+                [[maybe_unused]] double bz = 0.0;
+                if constexpr (!kScw) {
+                    bz = bf * iz;
+                    ur = u - bz;
+                }
                 const bool in = minX <= u && u < maxX && minY <= v && v < maxY;
                 if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
                 if (zc == 0.0) break;  // not in the image (in is false), whatever xc and yc are
@@ -124,8 +149,14 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                 const double Mu = fabs(fxx) + fabs(cx), Mv = fabs(fyy) + fabs(cy);
                 Eu = fabs(fx) * Exn + 4.0 * eps * Mu;
                 Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
-                Eur = (Eu + fabs(bf) * Eiz) + 4.0 * eps * (fabs(bz) + Mu);
-                if (!isfinite(((((u + v) + ur) + Eu) + Ev) + Eur)) {
+                double sum;  // finite when everything phase 2 reads is
+                if constexpr (kScw) {
+                    sum = ((u + v) + Eu) + Ev;
+                } else {
+                    Eur = (Eu + fabs(bf) * Eiz) + 4.0 * eps * (fabs(bz) + Mu);
+                    sum = ((((u + v) + ur) + Eu) + Ev) + Eur;
+                }
+                if (!isfinite(sum)) {
                     st = ORBFE_FUSE_MARGINAL;
                     break;
                 }
@@ -154,7 +185,7 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                     st = ORBFE_FUSE_MARGINAL;
                     break;
                 }
-                if (fu_near_int(q, 10.0 * eps / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
+                if (near_int(q, 10.0 * eps / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
                 const double cq = ceil(q);
                 const int level = cq < 0.0 ? 0 : (cq > (double)(levels - 1) ? levels - 1 : (int)cq);
                 r = th * scale[level];
@@ -166,7 +197,7 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                 }
                 const double Ewx = fabs(winv) * (Eu + 4.0 * eps * ((fabs(u) + fabs(minX)) + fabs(r)));
                 const double Ewy = fabs(hinv) * (Ev + 4.0 * eps * ((fabs(v) + fabs(minY)) + fabs(r)));
-                if (fu_near_int(ax, Ewx) || fu_near_int(bx, Ewx) || fu_near_int(ay, Ewy) || fu_near_int(by, Ewy))
+                if (near_int(ax, Ewx) || near_int(bx, Ewx) || near_int(ay, Ewy) || near_int(by, Ewy))
                     st = ORBFE_FUSE_MARGINAL;
                 const double fax = floor(ax), cbx = ceil(bx), fay = floor(ay), cby = ceil(by);
                 // the four early returns of get_features_in_area
@@ -180,10 +211,12 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
         }
         s_u[tid] = u;
         s_v[tid] = v;
-        s_ur[tid] = ur;
         s_eu[tid] = Eu;
         s_ev[tid] = Ev;
-        s_eur[tid] = Eur;
+        if constexpr (!kScw) {
+            s_ur[tid] = ur;
+            s_eur[tid] = Eur;
+        }
         s_r[tid] = r;
         s_x0[tid] = (int16_t)x0;
         s_x1[tid] = (int16_t)x1;
@@ -193,32 +226,45 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
         s_st[tid] = (uint8_t)st;
     }
     __syncthreads();
-    // ---- phase 2: kFuGroup lanes per point
-    const int g = tid / kFuGroup, l = tid % kFuGroup;
+    // ---- phase 2: kPsGroup lanes per point
+    const int g = tid / kPsGroup, l = tid % kPsGroup;
     const int64_t base = kf.off[k];
     const double* xy = kf.xy + 2 * base;
-    const double* uright = kf.u_right + base;
     const int32_t* oct = kf.octave + base;
     const uint4* desc = reinterpret_cast<const uint4*>(kf.desc + base * 32);
     const int32_t* coff = kf.cell_off + kf.cell_at[k];
     const int32_t* cidx = kf.cell_idx + kf.idx_at[k];
-    const double* is2 = kf.inv_sigma2 + kf.lvl_off[k];
-    for (int j = g; j < kFuChunk; j += kFuChunk / kFuGroup) {
+    [[maybe_unused]] const double *uright = nullptr, *is2 = nullptr;
+    [[maybe_unused]] const uint8_t* blk = nullptr;
+    if constexpr (kScw) {
+        blk = kf.blocked ? kf.blocked + base : nullptr;
+    } else {
+        uright = kf.u_right + base;
+        is2 = kf.inv_sigma2 + kf.lvl_off[k];
+    }
+    for (int j = g; j < kPsChunk; j += kPsChunk / kPsGroup) {
         const int64_t i = first + j;
         if (i >= pt.n) break;
         const int level = s_lvl[j];
         unsigned st = s_st[j];
-        unsigned key = kFuNone;
+        unsigned key = kPsNone;
         if (level >= 0) {
-            const double u = s_u[j], v = s_v[j], ur = s_ur[j], Eu = s_eu[j], Ev = s_ev[j], Eur = s_eur[j], r = s_r[j];
+            const double u = s_u[j], v = s_v[j], Eu = s_eu[j], Ev = s_ev[j], r = s_r[j];
+            [[maybe_unused]] double ur = 0.0, Eur = 0.0;
+            if constexpr (!kScw) {
+                ur = s_ur[j];
+                Eur = s_eur[j];
+            }
             const int x0 = s_x0[j], x1 = s_x1[j], y0 = s_y0[j], y1 = s_y1[j];
             const uint4* pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
             const uint4 qa = pd[0], qb = pd[1];
             const double er_r = eps * fabs(r);
             for (int ix = x0; ix <= x1; ++ix) {
                 const int a = coff[ix * rows + y0], b = coff[ix * rows + y1 + 1];
-                for (int pos = a + l; pos < b; pos += kFuGroup) {
+                for (int pos = a + l; pos < b; pos += kPsGroup) {
                     const int f = cidx[pos];
+                    if constexpr (kScw)
+                        if (blk && blk[f]) continue;
                     const double kx = xy[2 * f], ky = xy[2 * f + 1];
                     const double dx = kx - u, dy = ky - v;
                     const double Edx = Eu + 2.0 * eps * (fabs(kx) + fabs(u)), Edy = Ev + 2.0 * eps * (fabs(ky) + fabs(v));
@@ -226,25 +272,27 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                     if (!(fabs(dx) < r && fabs(dy) < r)) continue;
                     const int o = oct[f];
                     if (o < level - 1 || o > level) continue;
-                    const double kr = uright[f];
-                    const double ex = u - kx, ey = v - ky;
-                    const double bxy = (2.0 * fabs(ex) * Edx + Edx * Edx) + (2.0 * fabs(ey) * Edy + Edy * Edy);
-                    double e2, B, T;
-                    if (kr >= 0.0) {
-                        const double er = ur - kr;
-                        const double Eer = Eur + 2.0 * eps * (fabs(kr) + fabs(ur));
-                        e2 = (ex * ex + ey * ey) + er * er;
-                        B = bxy + (2.0 * fabs(er) * Eer + Eer * Eer);
-                        T = 7.8;
-                    } else {
-                        e2 = ex * ex + ey * ey;
-                        B = bxy;
-                        T = 5.99;
+                    if constexpr (!kScw) {
+                        const double kr = uright[f];
+                        const double ex = u - kx, ey = v - ky;
+                        const double bxy = (2.0 * fabs(ex) * Edx + Edx * Edx) + (2.0 * fabs(ey) * Edy + Edy * Edy);
+                        double e2, B, T;
+                        if (kr >= 0.0) {
+                            const double er = ur - kr;
+                            const double Eer = Eur + 2.0 * eps * (fabs(kr) + fabs(ur));
+                            e2 = (ex * ex + ey * ey) + er * er;
+                            B = bxy + (2.0 * fabs(er) * Eer + Eer * Eer);
+                            T = 7.8;
+                        } else {
+                            e2 = ex * ex + ey * ey;
+                            B = bxy;
+                            T = 5.99;
+                        }
+                        const double chi = e2 * is2[o];
+                        const double Echi = fabs(is2[o]) * B + 6.0 * eps * fabs(chi);
+                        if (!(fabs(chi - T) >= Echi + eps * T)) st = ORBFE_FUSE_MARGINAL;  // a NaN marks too
+                        if (chi > T) continue;
                     }
-                    const double chi = e2 * is2[o];
-                    const double Echi = fabs(is2[o]) * B + 6.0 * eps * fabs(chi);
-                    if (!(fabs(chi - T) >= Echi + eps * T)) st = ORBFE_FUSE_MARGINAL;  // a NaN marks too
-                    if (chi > T) continue;
                     const uint4 da = desc[2 * f], db = desc[2 * f + 1];
                     const unsigned d = __popc(da.x ^ qa.x) + __popc(da.y ^ qa.y) + __popc(da.z ^ qa.z) +
                                        __popc(da.w ^ qa.w) + __popc(db.x ^ qb.x) + __popc(db.y ^ qb.y) +
@@ -253,29 +301,38 @@ __global__ __launch_bounds__(kFuChunk) void k_fuse_search(FuKfs kf, FuPts pt, do
                 }
             }
 #pragma unroll
-            for (int o = kFuGroup / 2; o; o >>= 1) {
-                key = min(key, (unsigned)__shfl_xor((int)key, o, kFuGroup));
-                st |= (unsigned)__shfl_xor((int)st, o, kFuGroup);
+            for (int o = kPsGroup / 2; o; o >>= 1) {
+                key = min(key, (unsigned)__shfl_xor((int)key, o, kPsGroup));
+                st |= (unsigned)__shfl_xor((int)st, o, kPsGroup);
             }
         }
         if (l == 0) {
             const int64_t at = (int64_t)k * out.stride + i;
-            out.best_idx[at] = key == kFuNone ? -1 : cidx[key & 0xFFFFu];
-            out.best_dist[at] = key == kFuNone ? -1 : (int)(key >> 16);
+            out.best_idx[at] = key == kPsNone ? -1 : cidx[key & 0xFFFFu];
+            out.best_dist[at] = key == kPsNone ? -1 : (int)(key >> 16);
             out.status[at] = (uint8_t)st;
         }
     }
+}
+
+__global__ __launch_bounds__(kPsChunk) void k_fuse_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out) {
+    proj_search<false>(kf, pt, th, eps, out);
+}
+
+__global__ __launch_bounds__(kPsChunk) void k_scw_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out) {
+    proj_search<true>(kf, pt, th, eps, out);
 }
 
 }  // namespace orbfe
 
 namespace {
 
-// scratch of orbfe_fuse_search: process-wide, created on first use and never torn down (the HIP runtime may
-// already be gone when static destructors run); callers on several threads take turns
-struct Fuser {
+// scratch of one entry: process-wide, created on first use and never torn down (the HIP runtime may already be gone
+// when static destructors run); callers of that entry on several threads take turns.  Each entry has an instance of
+// its own, so the two do not wait for each other and each last_ms is its own entry's.
+struct Searcher {
     std::mutex mu;
-    DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, status
+    DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, blocked bytes, status
     DevBuf<double> d_f64;   // keyframe scalars, xy, u_right, scale, inv_sigma2, point scalars
     DevBuf<int64_t> d_i64;  // off, cell_at, idx_at, lvl_off
     DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, best_idx, best_dist
@@ -285,8 +342,9 @@ struct Fuser {
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.f;
 };
-Fuser& fuser() {
-    static Fuser* m = new Fuser;
+template <bool kScw>
+Searcher& searcher() {
+    static Searcher* m = new Searcher;
     return *m;
 }
 
@@ -300,6 +358,171 @@ bool all_finite(const double* v, int64_t n) {
 
 size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
+// Both entries: validate, stage, launch, download.  kScw: u_right and inv_sigma2 are not looked at, slot 4 of a
+// keyframe's scalars may hold anything, and blocked may be null (nothing is blocked).  Otherwise blocked is not
+// looked at.  Out is the entry's orbfe_*_out.
+template <bool kScw, class Out>
+void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy, const int32_t* octave,
+            const double* u_right, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+            const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+            const double* scale, const double* inv_sigma2, int32_t n_kf, const double* pt_f64,
+            const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride) {
+    if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
+    if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
+    if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
+        throw Error(ORBFE_EINVAL, "th and eps must be finite and eps not negative");
+    if (n_kf == 0 || n_pts == 0) return;
+    if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale ||
+        (!kScw && !inv_sigma2) || !pt_f64 || !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
+        throw Error(ORBFE_EINVAL, "null argument");
+    if (out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
+    if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
+        throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
+    for (int32_t k = 0; k < n_kf; ++k)
+        if (off[k + 1] < off[k] || cell_at[k + 1] < cell_at[k] || idx_at[k + 1] < idx_at[k] ||
+            lvl_off[k + 1] < lvl_off[k])
+            throw Error(ORBFE_EINVAL, at_kf(k, "offsets must not decrease"));
+    for (int32_t k = 0; k < n_kf; ++k) {
+        const int64_t n = off[k + 1] - off[k], nc = cell_at[k + 1] - cell_at[k], ni = idx_at[k + 1] - idx_at[k],
+                      nl = lvl_off[k + 1] - lvl_off[k];
+        if (n > ORBFE_BOW_MAX_FRAME || ni > ORBFE_BOW_MAX_FRAME)
+            throw Error(ORBFE_EINVAL, at_kf(k, "more features or grid entries than the limit of " +
+                                                   std::to_string(ORBFE_BOW_MAX_FRAME) + " per keyframe"));
+        // slot 4 is bf, which k_scw_search does not read
+        const double* Kk = kf_f64 + (int64_t)k * ORBFE_FUSE_KF_F64;
+        if (!(all_finite(Kk, 4) && (kScw || std::isfinite(Kk[4])) && all_finite(Kk + 5, ORBFE_FUSE_KF_F64 - 5)))
+            throw Error(ORBFE_EINVAL, at_kf(k, "a scalar is not finite"));
+        const int64_t cols = kf_i32[3 * k], rows = kf_i32[3 * k + 1], levels = kf_i32[3 * k + 2];
+        if (levels <= 0) throw Error(ORBFE_EINVAL, at_kf(k, "the level count must be positive"));
+        if (nl != levels) throw Error(ORBFE_EINVAL, at_kf(k, "the level table does not have one entry per level"));
+        if (cols <= 0 || rows <= 0 || cols > 4096 || rows > 4096)
+            throw Error(ORBFE_EINVAL, at_kf(k, "grid columns and rows must lie in [1, 4096]"));
+        if (nc != cols * rows + 1) throw Error(ORBFE_EINVAL, at_kf(k, "the grid needs columns * rows + 1 cell offsets"));
+        if (!(all_finite(scale + lvl_off[k], nl) && (kScw || all_finite(inv_sigma2 + lvl_off[k], nl))))
+            throw Error(ORBFE_EINVAL, at_kf(k, "a level table entry is not finite"));
+        if (n > 0 && (!xy || !octave || (!kScw && !u_right) || !desc32)) throw Error(ORBFE_EINVAL, "null argument");
+        if (n > 0 && !(all_finite(xy + 2 * off[k], 2 * n) && (kScw || all_finite(u_right + off[k], n))))
+            throw Error(ORBFE_EINVAL, at_kf(k, "a keypoint coordinate is not finite"));
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t o = octave[off[k] + i];
+            if (o < 0 || o >= levels) throw Error(ORBFE_EINVAL, at_kf(k, "an octave is outside the level table"));
+        }
+        const int32_t* co = cell_off + cell_at[k];
+        if (co[0] != 0) throw Error(ORBFE_EINVAL, at_kf(k, "the first cell offset must be 0"));
+        for (int64_t c = 0; c < nc - 1; ++c)
+            if (co[c + 1] < co[c]) throw Error(ORBFE_EINVAL, at_kf(k, "cell offsets must not decrease"));
+        if (co[nc - 1] != ni) throw Error(ORBFE_EINVAL, at_kf(k, "the last cell offset is not the grid entry count"));
+        if (ni > 0 && !cell_idx) throw Error(ORBFE_EINVAL, "null argument");
+        for (int64_t e = 0; e < ni; ++e) {
+            const int32_t f = cell_idx[idx_at[k] + e];
+            if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
+        }
+    }
+    if (!all_finite(pt_f64, n_pts * ORBFE_FUSE_PT_F64)) throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+    const size_t nk = (size_t)n_kf, np = (size_t)n_pts, os = (size_t)out_stride;
+    const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
+                 nl = (size_t)lvl_off[n_kf];
+    // what only one variant stages has no room in the other's buffers
+    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kScw ? pad16(n) : 0;
+    const bool has_blocked = kScw && blocked != nullptr && n > 0;
+    Searcher& m = searcher<kScw>();
+    std::lock_guard<std::mutex> lk(m.mu);
+    if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : m.ev)
+        if (!e) HIPCK(hipEventCreate(&e));
+    hipStream_t s = m.stream;
+    // descriptors are read as uint4: both blocks start on 16 bytes
+    m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + n_blk + nk * os);
+    m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64);
+    m.d_i64.ensure(4 * (nk + 1));
+    m.d_i32.ensure(3 * nk + n + nc + ni + 2 * nk * os);
+    uint8_t* d_desc = m.d_u8.p;
+    uint8_t* d_pdesc = d_desc + pad16(n * 32);
+    uint8_t* d_blk = d_pdesc + pad16(np * 32);
+    uint8_t* d_st = d_blk + n_blk;
+    double* d_kf = m.d_f64.p;
+    double* d_xy = d_kf + nk * ORBFE_FUSE_KF_F64;
+    double* d_ur = d_xy + 2 * n;
+    double* d_scale = d_ur + n_ur;
+    double* d_is2 = d_scale + nl;
+    double* d_pt = d_is2 + n_is2;
+    int64_t* d_off = m.d_i64.p;
+    int64_t* d_cat = d_off + nk + 1;
+    int64_t* d_iat = d_cat + nk + 1;
+    int64_t* d_lvl = d_iat + nk + 1;
+    int32_t* d_ki = m.d_i32.p;
+    int32_t* d_oct = d_ki + 3 * nk;
+    int32_t* d_coff = d_oct + n;
+    int32_t* d_cidx = d_coff + nc;
+    int32_t* d_bi = d_cidx + ni;
+    int32_t* d_bd = d_bi + nk * os;
+    auto up = [&](void* dst, const void* src, size_t bytes) {
+        if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    };
+    up(d_desc, desc32, n * 32);
+    up(d_pdesc, pt_desc32, np * 32);
+    if (has_blocked) up(d_blk, blocked, n);
+    up(d_kf, kf_f64, nk * ORBFE_FUSE_KF_F64 * sizeof(double));
+    up(d_xy, xy, 2 * n * sizeof(double));
+    up(d_ur, u_right, n_ur * sizeof(double));
+    up(d_scale, scale, nl * sizeof(double));
+    up(d_is2, inv_sigma2, n_is2 * sizeof(double));
+    up(d_pt, pt_f64, np * ORBFE_FUSE_PT_F64 * sizeof(double));
+    up(d_off, off, (nk + 1) * sizeof(int64_t));
+    up(d_cat, cell_at, (nk + 1) * sizeof(int64_t));
+    up(d_iat, idx_at, (nk + 1) * sizeof(int64_t));
+    up(d_lvl, lvl_off, (nk + 1) * sizeof(int64_t));
+    up(d_ki, kf_i32, 3 * nk * sizeof(int32_t));
+    up(d_oct, octave, n * sizeof(int32_t));
+    up(d_coff, cell_off, nc * sizeof(int32_t));
+    up(d_cidx, cell_idx, ni * sizeof(int32_t));
+    PsKfs kf{};
+    kf.f64 = d_kf;
+    kf.i32 = d_ki;
+    kf.off = d_off;
+    kf.cell_at = d_cat;
+    kf.idx_at = d_iat;
+    kf.lvl_off = d_lvl;
+    kf.xy = d_xy;
+    kf.scale = d_scale;
+    kf.u_right = kScw ? nullptr : d_ur;
+    kf.inv_sigma2 = kScw ? nullptr : d_is2;
+    kf.octave = d_oct;
+    kf.cell_off = d_coff;
+    kf.cell_idx = d_cidx;
+    kf.desc = d_desc;
+    kf.blocked = has_blocked ? d_blk : nullptr;
+    const PsPts pt{d_pt, d_pdesc, n_pts};
+    const PsOut d{d_bi, d_bd, d_st, out_stride};
+    const unsigned chunks = (unsigned)((np + kPsChunk - 1) / kPsChunk);
+    HIPCK(hipEventRecord(m.ev[0], s));
+    constexpr auto kernel = kScw ? k_scw_search : k_fuse_search;
+    hipLaunchKernelGGL(kernel, dim3(chunks, (unsigned)n_kf), dim3(kPsChunk), 0, s, kf, pt, th, eps, d);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(m.ev[1], s));
+    // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
+    // the caller's arrays
+    m.h_i32.resize(2 * nk * os);
+    m.h_st.resize(nk * os);
+    HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * nk * os * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, nk * os, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+    for (size_t k = 0; k < nk; ++k) {
+        std::memcpy(out->best_idx + k * os, &m.h_i32[k * os], np * sizeof(int32_t));
+        std::memcpy(out->best_dist + k * os, &m.h_i32[nk * os + k * os], np * sizeof(int32_t));
+        std::memcpy(out->status + k * os, &m.h_st[k * os], np);
+    }
+}
+
+template <bool kScw>
+void last_ms(float* ms) {
+    if (!ms) throw Error(ORBFE_EINVAL, "null argument");
+    Searcher& m = searcher<kScw>();
+    std::lock_guard<std::mutex> lk(m.mu);
+    *ms = m.last_ms;
+}
+
 }  // namespace
 
 extern "C" {
@@ -311,154 +534,28 @@ int orbfe_fuse_search(const double* kf_f64, const int32_t* kf_i32, const int64_t
                       const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const orbfe_fuse_out* out,
                       int64_t out_stride) {
     return guarded([&] {
-        if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
-        if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
-        if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
-            throw Error(ORBFE_EINVAL, "th and eps must be finite and eps not negative");
-        if (n_kf == 0 || n_pts == 0) return;
-        if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale || !inv_sigma2 ||
-            !pt_f64 || !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
-            throw Error(ORBFE_EINVAL, "null argument");
-        if (out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
-        if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
-            throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
-        for (int32_t k = 0; k < n_kf; ++k)
-            if (off[k + 1] < off[k] || cell_at[k + 1] < cell_at[k] || idx_at[k + 1] < idx_at[k] ||
-                lvl_off[k + 1] < lvl_off[k])
-                throw Error(ORBFE_EINVAL, at_kf(k, "offsets must not decrease"));
-        for (int32_t k = 0; k < n_kf; ++k) {
-            const int64_t n = off[k + 1] - off[k], nc = cell_at[k + 1] - cell_at[k], ni = idx_at[k + 1] - idx_at[k],
-                          nl = lvl_off[k + 1] - lvl_off[k];
-            if (n > ORBFE_BOW_MAX_FRAME || ni > ORBFE_BOW_MAX_FRAME)
-                throw Error(ORBFE_EINVAL, at_kf(k, "more features or grid entries than the limit of " +
-                                                       std::to_string(ORBFE_BOW_MAX_FRAME) + " per keyframe"));
-            if (!all_finite(kf_f64 + (int64_t)k * ORBFE_FUSE_KF_F64, ORBFE_FUSE_KF_F64))
-                throw Error(ORBFE_EINVAL, at_kf(k, "a scalar is not finite"));
-            const int64_t cols = kf_i32[3 * k], rows = kf_i32[3 * k + 1], levels = kf_i32[3 * k + 2];
-            if (levels <= 0) throw Error(ORBFE_EINVAL, at_kf(k, "the level count must be positive"));
-            if (nl != levels) throw Error(ORBFE_EINVAL, at_kf(k, "the level tables do not have one entry per level"));
-            if (cols <= 0 || rows <= 0 || cols > 4096 || rows > 4096)
-                throw Error(ORBFE_EINVAL, at_kf(k, "grid columns and rows must lie in [1, 4096]"));
-            if (nc != cols * rows + 1)
-                throw Error(ORBFE_EINVAL, at_kf(k, "the grid needs columns * rows + 1 cell offsets"));
-            if (!(all_finite(scale + lvl_off[k], nl) && all_finite(inv_sigma2 + lvl_off[k], nl)))
-                throw Error(ORBFE_EINVAL, at_kf(k, "a level table entry is not finite"));
-            if (n > 0 && (!xy || !octave || !u_right || !desc32)) throw Error(ORBFE_EINVAL, "null argument");
-            if (n > 0 && !(all_finite(xy + 2 * off[k], 2 * n) && all_finite(u_right + off[k], n)))
-                throw Error(ORBFE_EINVAL, at_kf(k, "a keypoint coordinate is not finite"));
-            for (int64_t i = 0; i < n; ++i) {
-                const int32_t o = octave[off[k] + i];
-                if (o < 0 || o >= levels) throw Error(ORBFE_EINVAL, at_kf(k, "an octave is outside the level table"));
-            }
-            const int32_t* co = cell_off + cell_at[k];
-            if (co[0] != 0) throw Error(ORBFE_EINVAL, at_kf(k, "the first cell offset must be 0"));
-            for (int64_t c = 0; c < nc - 1; ++c)
-                if (co[c + 1] < co[c]) throw Error(ORBFE_EINVAL, at_kf(k, "cell offsets must not decrease"));
-            if (co[nc - 1] != ni) throw Error(ORBFE_EINVAL, at_kf(k, "the last cell offset is not the grid entry count"));
-            if (ni > 0 && !cell_idx) throw Error(ORBFE_EINVAL, "null argument");
-            for (int64_t e = 0; e < ni; ++e) {
-                const int32_t f = cell_idx[idx_at[k] + e];
-                if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
-            }
-        }
-        if (!all_finite(pt_f64, n_pts * ORBFE_FUSE_PT_F64)) throw Error(ORBFE_EINVAL, "a point scalar is not finite");
-        const size_t nk = (size_t)n_kf, np = (size_t)n_pts, os = (size_t)out_stride;
-        const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
-                     nl = (size_t)lvl_off[n_kf];
-        Fuser& m = fuser();
-        std::lock_guard<std::mutex> lk(m.mu);
-        if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : m.ev)
-            if (!e) HIPCK(hipEventCreate(&e));
-        hipStream_t s = m.stream;
-        // descriptors are read as uint4: both blocks start on 16 bytes
-        m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + nk * os);
-        m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 3 * n + 2 * nl + np * ORBFE_FUSE_PT_F64);
-        m.d_i64.ensure(4 * (nk + 1));
-        m.d_i32.ensure(3 * nk + n + nc + ni + 2 * nk * os);
-        uint8_t* d_desc = m.d_u8.p;
-        uint8_t* d_pdesc = d_desc + pad16(n * 32);
-        uint8_t* d_st = d_pdesc + pad16(np * 32);
-        double* d_kf = m.d_f64.p;
-        double* d_xy = d_kf + nk * ORBFE_FUSE_KF_F64;
-        double* d_ur = d_xy + 2 * n;
-        double* d_scale = d_ur + n;
-        double* d_is2 = d_scale + nl;
-        double* d_pt = d_is2 + nl;
-        int64_t* d_off = m.d_i64.p;
-        int64_t* d_cat = d_off + nk + 1;
-        int64_t* d_iat = d_cat + nk + 1;
-        int64_t* d_lvl = d_iat + nk + 1;
-        int32_t* d_ki = m.d_i32.p;
-        int32_t* d_oct = d_ki + 3 * nk;
-        int32_t* d_coff = d_oct + n;
-        int32_t* d_cidx = d_coff + nc;
-        int32_t* d_bi = d_cidx + ni;
-        int32_t* d_bd = d_bi + nk * os;
-        auto up = [&](void* dst, const void* src, size_t bytes) {
-            if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-        };
-        up(d_desc, desc32, n * 32);
-        up(d_pdesc, pt_desc32, np * 32);
-        up(d_kf, kf_f64, nk * ORBFE_FUSE_KF_F64 * sizeof(double));
-        up(d_xy, xy, 2 * n * sizeof(double));
-        up(d_ur, u_right, n * sizeof(double));
-        up(d_scale, scale, nl * sizeof(double));
-        up(d_is2, inv_sigma2, nl * sizeof(double));
-        up(d_pt, pt_f64, np * ORBFE_FUSE_PT_F64 * sizeof(double));
-        up(d_off, off, (nk + 1) * sizeof(int64_t));
-        up(d_cat, cell_at, (nk + 1) * sizeof(int64_t));
-        up(d_iat, idx_at, (nk + 1) * sizeof(int64_t));
-        up(d_lvl, lvl_off, (nk + 1) * sizeof(int64_t));
-        up(d_ki, kf_i32, 3 * nk * sizeof(int32_t));
-        up(d_oct, octave, n * sizeof(int32_t));
-        up(d_coff, cell_off, nc * sizeof(int32_t));
-        up(d_cidx, cell_idx, ni * sizeof(int32_t));
-        FuKfs kf{};
-        kf.f64 = d_kf;
-        kf.i32 = d_ki;
-        kf.off = d_off;
-        kf.cell_at = d_cat;
-        kf.idx_at = d_iat;
-        kf.lvl_off = d_lvl;
-        kf.xy = d_xy;
-        kf.u_right = d_ur;
-        kf.scale = d_scale;
-        kf.inv_sigma2 = d_is2;
-        kf.octave = d_oct;
-        kf.cell_off = d_coff;
-        kf.cell_idx = d_cidx;
-        kf.desc = d_desc;
-        const FuPts pt{d_pt, d_pdesc, n_pts};
-        const FuOut d{d_bi, d_bd, d_st, out_stride};
-        const unsigned chunks = (unsigned)((np + kFuChunk - 1) / kFuChunk);
-        HIPCK(hipEventRecord(m.ev[0], s));
-        hipLaunchKernelGGL(k_fuse_search, dim3(chunks, (unsigned)n_kf), dim3(kFuChunk), 0, s, kf, pt, th, eps, d);
-        HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(m.ev[1], s));
-        // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
-        // the caller's arrays
-        m.h_i32.resize(2 * nk * os);
-        m.h_st.resize(nk * os);
-        HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * nk * os * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, nk * os, hipMemcpyDeviceToHost, s));
-        HIPCK(hipStreamSynchronize(s));
-        HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
-        for (size_t k = 0; k < nk; ++k) {
-            std::memcpy(out->best_idx + k * os, &m.h_i32[k * os], np * sizeof(int32_t));
-            std::memcpy(out->best_dist + k * os, &m.h_i32[nk * os + k * os], np * sizeof(int32_t));
-            std::memcpy(out->status + k * os, &m.h_st[k * os], np);
-        }
+        search<false>(kf_f64, kf_i32, off, xy, octave, u_right, desc32, nullptr, cell_at, cell_off, idx_at, cell_idx,
+                      lvl_off, scale, inv_sigma2, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, out_stride);
     });
 }
 
 int orbfe_fuse_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<false>(ms); });
+}
+
+int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                     const int32_t* octave, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+                     const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                     const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                     double th, double eps, const orbfe_scw_out* out, int64_t out_stride) {
     return guarded([&] {
-        if (!ms) throw Error(ORBFE_EINVAL, "null argument");
-        Fuser& m = fuser();
-        std::lock_guard<std::mutex> lk(m.mu);
-        *ms = m.last_ms;
+        search<true>(kf_f64, kf_i32, off, xy, octave, nullptr, desc32, blocked, cell_at, cell_off, idx_at, cell_idx,
+                     lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, out_stride);
     });
+}
+
+int orbfe_scw_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<true>(ms); });
 }
 
 }  // extern "C"

@@ -607,15 +607,10 @@ def _tri_epipole(ex, ey, f2):
     return x, y
 
 
-def fuse_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
-                       scale, inv_sigma2, pt_f64, pt_desc, th, eps) -> dict:
-    """orbfe_fuse_search (k_fuse_search, include/orbfe.h): the search half of ORBMatcher.fuse_pkf_mp
-    (ORBMatcher.py:498-567) for every (keyframe, point) in one launch.  kf_f64 (K, 27) and kf_i32 (K, 3) hold the
-    keyframes' scalars; keyframe k is features [off[k], off[k + 1]) of xy (x 2 f64) / octave (i32) / u_right (f64,
-    negative: mono) / desc (x 32 u8), cell offsets [cell_at[k], cell_at[k + 1]) of cell_off, grid entries
-    [idx_at[k], idx_at[k + 1]) of cell_idx and levels [lvl_off[k], lvl_off[k + 1]) of scale / inv_sigma2; pt_f64
-    (P, 9) and pt_desc (P, 32) are the points.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
-    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
+def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off, scale,
+                   pt_f64, pt_desc, th, eps, u_right=None, inv_sigma2=None, blocked=None) -> dict:
+    """fuse_search_arrays (fuse, with u_right and inv_sigma2) and scw_search_arrays (not fuse, with blocked or
+    None): the conversion, the length checks, the outputs and the call."""
     def arr(a, dt):
         return None if a is None else np.ascontiguousarray(a, dt)
     kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
@@ -624,46 +619,6 @@ def fuse_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, cell_at, 
     pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
     off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
     xy, u_right, scale, inv_sigma2 = (arr(a, np.float64) for a in (xy, u_right, scale, inv_sigma2))
-    octave, cell_off, cell_idx, desc = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32), arr(
-        desc, np.uint8)
-    n_kf, n_pts = len(kf_f64), len(pt_f64)
-    if len(kf_i32) != n_kf or len(pt_desc) != n_pts:
-        raise ValueError("kf_i32 / pt_desc do not cover the keyframes / points")
-    for a in (off, cell_at, idx_at, lvl_off):
-        if a is None or len(a) != n_kf + 1:
-            raise ValueError("an offset array does not have one entry per keyframe and one more")
-    if n_kf:
-        n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
-        for a, need in ((xy, 2 * n), (octave, n), (u_right, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni),
-                        (scale, nl), (inv_sigma2, nl)):
-            if need > 0 and (a is None or a.size < need):
-                raise ValueError("a per-keyframe array is shorter than its offsets say")
-    bi = np.full((n_kf, n_pts), -1, np.int32)
-    bd = np.full((n_kf, n_pts), -1, np.int32)
-    st = np.zeros((n_kf, n_pts), np.uint8)
-    out = _lib.FuseOut(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
-    call("orbfe_fuse_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(u_right), ptr(desc),
-         ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), ptr(inv_sigma2), n_kf,
-         ptr(pt_f64), ptr(pt_desc), n_pts, float(th), float(eps), C.byref(out), n_pts)
-    return dict(best_idx=bi, best_dist=bd, status=st)
-
-
-def scw_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, cell_off, idx_at, cell_idx, lvl_off,
-                      scale, pt_f64, pt_desc, th, eps) -> dict:
-    """orbfe_scw_search (k_scw_search, include/orbfe.h): the search half of ORBMatcher.fuse_kf_scw_mp
-    (ORBMatcher.py:409-468) and of search_by_projection_ckf_scw_mp (:863-916) for every (keyframe, point) in one
-    launch.  The arrays are fuse_search_arrays' without u_right and inv_sigma2; the pose slots of kf_f64 hold what
-    the Sim3 gives and its bf slot is not read.  blocked: None, or one byte per feature (concatenated at `off`),
-    non-zero for a feature that is no candidate.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
-    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
-    def arr(a, dt):
-        return None if a is None else np.ascontiguousarray(a, dt)
-    kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
-    kf_i32 = np.ascontiguousarray(kf_i32, np.int32).reshape(-1, 3)
-    pt_f64 = np.ascontiguousarray(pt_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
-    pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
-    off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
-    xy, scale = arr(xy, np.float64), arr(scale, np.float64)
     octave, cell_off, cell_idx = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32)
     desc, blocked = arr(desc, np.uint8), arr(blocked, np.uint8)
     n_kf, n_pts = len(kf_f64), len(pt_f64)
@@ -674,19 +629,52 @@ def scw_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, c
             raise ValueError("an offset array does not have one entry per keyframe and one more")
     if n_kf:
         n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
-        for a, need in ((xy, 2 * n), (octave, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni), (scale, nl)):
-            if need > 0 and (a is None or a.size < need):
+        need = [(xy, 2 * n), (octave, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni), (scale, nl)]
+        if fuse:
+            need += [(u_right, n), (inv_sigma2, nl)]
+        for a, size in need:
+            if size > 0 and (a is None or a.size < size):
                 raise ValueError("a per-keyframe array is shorter than its offsets say")
         if blocked is not None and blocked.size < n:
             raise ValueError("blocked does not have one byte per feature")
     bi = np.full((n_kf, n_pts), -1, np.int32)
     bd = np.full((n_kf, n_pts), -1, np.int32)
     st = np.zeros((n_kf, n_pts), np.uint8)
-    out = _lib.ScwOut(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
-    call("orbfe_scw_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(desc), ptr(blocked),
-         ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), n_kf, ptr(pt_f64),
-         ptr(pt_desc), n_pts, float(th), float(eps), C.byref(out), n_pts)
+    out = (_lib.FuseOut if fuse else _lib.ScwOut)(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data,
+                                                  status=st.ctypes.data)
+    grid = (ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale))
+    if fuse:
+        entry, kf = "orbfe_fuse_search", (ptr(xy), ptr(octave), ptr(u_right), ptr(desc)) + grid + (ptr(inv_sigma2),)
+    else:
+        entry, kf = "orbfe_scw_search", (ptr(xy), ptr(octave), ptr(desc), ptr(blocked)) + grid
+    call(entry, ptr(kf_f64), ptr(kf_i32), ptr(off), *kf, n_kf, ptr(pt_f64), ptr(pt_desc), n_pts, float(th),
+         float(eps), C.byref(out), n_pts)
     return dict(best_idx=bi, best_dist=bd, status=st)
+
+
+def fuse_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                       scale, inv_sigma2, pt_f64, pt_desc, th, eps) -> dict:
+    """orbfe_fuse_search (k_fuse_search, include/orbfe.h): the search half of ORBMatcher.fuse_pkf_mp
+    (ORBMatcher.py:498-567) for every (keyframe, point) in one launch.  kf_f64 (K, 27) and kf_i32 (K, 3) hold the
+    keyframes' scalars; keyframe k is features [off[k], off[k + 1]) of xy (x 2 f64) / octave (i32) / u_right (f64,
+    negative: mono) / desc (x 32 u8), cell offsets [cell_at[k], cell_at[k + 1]) of cell_off, grid entries
+    [idx_at[k], idx_at[k + 1]) of cell_idx and levels [lvl_off[k], lvl_off[k + 1]) of scale / inv_sigma2; pt_f64
+    (P, 9) and pt_desc (P, 32) are the points.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
+    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
+    return _search_arrays(True, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                          scale, pt_f64, pt_desc, th, eps, u_right=u_right, inv_sigma2=inv_sigma2)
+
+
+def scw_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                      scale, pt_f64, pt_desc, th, eps) -> dict:
+    """orbfe_scw_search (k_scw_search, include/orbfe.h): the search half of ORBMatcher.fuse_kf_scw_mp
+    (ORBMatcher.py:409-468) and of search_by_projection_ckf_scw_mp (:863-916) for every (keyframe, point) in one
+    launch.  The arrays are fuse_search_arrays' without u_right and inv_sigma2; the pose slots of kf_f64 hold what
+    the Sim3 gives and its bf slot is not read.  blocked: None, or one byte per feature (concatenated at `off`),
+    non-zero for a feature that is no candidate.  Returns best_idx, best_dist (K, P) int32 (-1: no candidate) and
+    status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
+    return _search_arrays(False, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                          scale, pt_f64, pt_desc, th, eps, blocked=blocked)
 
 
 # eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
@@ -1570,7 +1558,7 @@ class ORBMatcher:
         return f, (Rcw, tcw, Ow)
 
     @staticmethod
-    def _scw_points(vpPoints, skip):
+    def _search_points(vpPoints, skip):
         """The points once: (slot per list position, rows, descriptor rows, any float32).  slot >= 0 is the row sent
         to the device, -1 not expressible (_fuse_point), -2 skipped by skip(pMP)."""
         slot, rows, descs, f32 = [], [], [], False
@@ -1589,18 +1577,22 @@ class ORBMatcher:
         return slot, rows, descs, f32
 
     @staticmethod
-    def _scw_launch(fr, blocked, rows, descs, th, f32):
+    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None):
+        """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse) or of
+        scw_search_arrays (with blocked)."""
         def offs(lens):
             o = np.zeros(len(fr) + 1, np.int64)
             np.cumsum(lens, out=o[1:])
             return o
         cat = lambda name: np.concatenate([getattr(f, name) for f in fr])  # noqa: E731
-        return scw_search_arrays(np.stack([f.f64 for f in fr]), np.stack([f.i32 for f in fr]),
-                                 offs([len(f.xy) for f in fr]), cat("xy"), cat("octave"), cat("desc"), blocked,
-                                 offs([len(f.cell_off) for f in fr]), cat("cell_off"),
-                                 offs([len(f.cell_idx) for f in fr]), cat("cell_idx"),
-                                 offs([len(f.scale) for f in fr]), cat("scale"), np.array(rows, np.float64),
-                                 np.stack(descs), th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+        head = (np.stack([f.f64 for f in fr]), np.stack([f.i32 for f in fr]), offs([len(f.xy) for f in fr]), cat("xy"),
+                cat("octave"))
+        grid = (offs([len(f.cell_off) for f in fr]), cat("cell_off"), offs([len(f.cell_idx) for f in fr]),
+                cat("cell_idx"), offs([len(f.scale) for f in fr]), cat("scale"))
+        pts = (np.array(rows, np.float64), np.stack(descs), th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+        if fuse:
+            return fuse_search_arrays(*head, cat("u_right"), cat("desc"), *grid, cat("inv_sigma2"), *pts)
+        return scw_search_arrays(*head, cat("desc"), blocked, *grid, *pts)
 
     def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
         """What this loop returns (LoopClosing.search_and_fuse, LoopClosing.py:352-367, with after = its replace
@@ -1645,12 +1637,12 @@ class ORBMatcher:
             return [whole(kf, Scw) for kf, Scw in zip(kfs, Scws)]
         frames = [self._scw_frame(kf, Scw, self._sim3_to_pose) for kf, Scw in zip(kfs, Scws)]
         live = [k for k, f in enumerate(frames) if f is not None]
-        slot, rows, descs, f32 = self._scw_points(vpPoints, _IS_BAD) if live else ([], [], [], False)
+        slot, rows, descs, f32 = self._search_points(vpPoints, _IS_BAD) if live else ([], [], [], False)
         res, snaps = None, []
         if live and rows:
             fr = [frames[k][0] for k in live]
             snaps = [d.tobytes() for d in descs]
-            res = self._scw_launch(fr, None, rows, descs, th, f32 or any(f.f32 for f in fr))
+            res = self._search_launch(fr, rows, descs, th, f32 or any(f.f32 for f in fr))
         slot_arr = np.array(slot, np.int64)
         alone = np.flatnonzero(slot_arr == -1)   # list positions whose point goes alone in every keyframe
         sent = np.flatnonzero(slot_arr >= 0)     # list positions in device row order
@@ -1812,40 +1804,14 @@ class ORBMatcher:
             return [self.fuse_pkf_mp(kf, vpMapPoints, th) for kf in kfs]
         frames = [_fuse_frame(kf) for kf in kfs]
         live = [k for k, f in enumerate(frames) if f is not None]
-        # the points once: slot >= 0 is the row sent to the device, -1 not expressible, -2 None or bad already
-        slot, rows, descs, snaps, f32 = [], [], [], [], False
-        if live:
-            for pMP in vpMapPoints:
-                if not pMP or pMP.is_bad():
-                    slot.append(-2)
-                    continue
-                pt = _fuse_point(pMP)
-                if pt is None:
-                    slot.append(-1)
-                    continue
-                slot.append(len(rows))
-                rows.append(pt[0])
-                descs.append(pt[1])
-                f32 = f32 or pt[2]
-        res = None
+        # the points once (slot -2: None or bad already), and none when no keyframe is expressible
+        skip = lambda p: not p or p.is_bad()  # noqa: E731
+        slot, rows, descs, f32 = self._search_points(vpMapPoints, skip) if live else ([], [], [], False)
+        res, snaps = None, []
         if live and rows:
             fr = [frames[k] for k in live]
-            f32 = f32 or any(f.f32 for f in fr)
-
-            def offs(lens):
-                o = np.zeros(len(fr) + 1, np.int64)
-                np.cumsum(lens, out=o[1:])
-                return o
-            cat = lambda name: np.concatenate([getattr(f, name) for f in fr])  # noqa: E731
-            pt_desc = np.stack(descs)
             snaps = [d.tobytes() for d in descs]
-            res = fuse_search_arrays(np.stack([f.f64 for f in fr]), np.stack([f.i32 for f in fr]),
-                                     offs([len(f.xy) for f in fr]), cat("xy"), cat("octave"), cat("u_right"),
-                                     cat("desc"), offs([len(f.cell_off) for f in fr]), cat("cell_off"),
-                                     offs([len(f.cell_idx) for f in fr]), cat("cell_idx"),
-                                     offs([len(f.scale) for f in fr]), cat("scale"), cat("inv_sigma2"),
-                                     np.array(rows, np.float64), pt_desc, th,
-                                     FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+            res = self._search_launch(fr, rows, descs, th, f32 or any(f.f32 for f in fr), fuse=True)
         slot_arr = np.array(slot, np.int64)
         alone = np.flatnonzero(slot_arr == -1)   # list positions whose point goes alone in every keyframe
         sent = np.flatnonzero(slot_arr >= 0)     # list positions in device row order
@@ -2164,11 +2130,11 @@ class ORBMatcher:
             vpPoints = list(vpPoints)
         spAlreadyFound = set(vpMatched) - {None}
         blocked = np.fromiter((m is not None for m in vpMatched), np.uint8, count=len(vpMatched))
-        slot, rows, descs, f32 = self._scw_points(vpPoints, lambda p: p.is_bad() or p in spAlreadyFound)
+        slot, rows, descs, f32 = self._search_points(vpPoints, lambda p: p.is_bad() or p in spAlreadyFound)
         slot_arr = np.array(slot, np.int64)
         todo = np.flatnonzero(slot_arr == -1)
         if rows:
-            res = self._scw_launch([f], blocked, rows, descs, th, f32 or f.f32)
+            res = self._search_launch([f], rows, descs, th, f32 or f.f32, blocked=blocked)
             bi, bd, st = res["best_idx"][0], res["best_dist"][0], res["status"][0]
             # what is left of a point's candidates is never closer than its best: above TH_LOW nothing is assigned
             sent = np.flatnonzero(slot_arr >= 0)

@@ -1,13 +1,16 @@
 """k_scw_search on the GPU: the host entry on every placed case against the array oracle, bit for bit on all three
 outputs and with guard rows around them, the reference's golden through the arrays, fuse_kf_scw_mp_many against loops
 of fuse_kf_scw_mp and against the golden, search_by_projection_ckf_scw_mp's device path against the golden and the
-host body, the per-item fallbacks of both, and concurrent callers."""
+host body, the per-item fallbacks of both, concurrent callers, and orbfe_fuse_search beside it: each entry's own last_ms
+and own scratch."""
 import ctypes as C
 import threading
 
 import numpy as np
 import pytest
 
+import fuse_cases as FC
+import fuse_oracle as FO
 import matcher_world as MW
 import scw_cases as SC
 import scw_oracle as SO
@@ -287,3 +290,58 @@ def test_four_threads_get_their_own_results():
     for t in ts:
         t.join()
     assert not errors, errors
+
+
+# ---- 6. the two entries share their code, not their state --------------------------------------------------------------
+def run_fuse(a):
+    from pyorbslam_amd.matcher import fuse_search_arrays
+    r = fuse_search_arrays(*[a[k] for k in FO.ARRAYS], a["th"], a["eps"])
+    return r["best_idx"], r["best_dist"], r["status"]
+
+
+def fuse_arrays(name, n_pts=None):
+    """The fuse entry's arrays of a case (its points cut to n_pts), and the scw entry's of the same case."""
+    case = dict(next(c for c in CASES if c["name"] == name))
+    if n_pts is not None:
+        case["pt_f64"], case["pt_desc"] = case["pt_f64"][:n_pts].copy(), case["pt_desc"][:n_pts].copy()
+    return FC.arrays(case), SC.arrays(case)
+
+
+def test_each_entry_keeps_its_own_last_ms():
+    """A launch of one entry leaves the other's last_ms as it was, bit for bit, in both directions."""
+    from pyorbslam_amd import _lib
+
+    def last_ms(entry):
+        ms = C.c_float(-1)
+        _lib.call(entry + "_last_ms", C.byref(ms))
+        return np.float32(ms.value).tobytes()
+    fuse, scw = fuse_arrays("ragged_2", 3)
+    for first, run_first, run_other, a, b in (("orbfe_fuse_search", run_fuse, run_host, fuse, scw),
+                                              ("orbfe_scw_search", run_host, run_fuse, scw, fuse)):
+        run_first(a)
+        before = last_ms(first)
+        assert np.frombuffer(before, np.float32)[0] > 0
+        run_other(b)
+        assert last_ms(first) == before, first
+
+
+def test_the_entries_run_side_by_side():
+    """One thread in fuse_search_arrays and one in scw_search_arrays at the same time, on different inputs: every
+    call returns what the same call returned alone."""
+    jobs = [(run_fuse, fuse_arrays("ragged_2")[0]), (run_host, fuse_arrays("ragged_9")[1])]
+    alone = [run(a) for run, a in jobs]
+    errors = []
+
+    def work(run, a, want):
+        try:
+            for _ in range(30):
+                assert_same(run(a), want, run.__name__ + " (side by side)")
+        except BaseException as e:  # noqa: BLE001
+            errors.append((run.__name__, repr(e)))
+    ts = [threading.Thread(target=work, args=(run, a, want)) for (run, a), want in zip(jobs, alone)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors, errors
+    assert_same(alone[1], ORACLE["ragged_9"], "ragged_9 alone")

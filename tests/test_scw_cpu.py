@@ -306,7 +306,10 @@ def test_table_and_header_agree():
     fields = re.search(r"typedef struct orbfe_scw_out \{(.*?)\}", code, flags=re.S).group(1)
     assert re.findall(r"\*\s*(\w+);", fields) == [f[0] for f in LIB.ScwOut._fields_]
     assert int(re.search(r"#define ORBFE_ABI_VERSION (\d+)", hdr).group(1)) == 9
-    assert "orbfe_scw.hip" in (ROOT / "Makefile").read_text()
+    # the Makefile builds the file that defines the entry
+    src = ROOT / "pyorbslam_amd" / "csrc" / "orbfe_fuse.hip"
+    assert re.search(r"^int orbfe_scw_search\s*\(", src.read_text(), flags=re.M)
+    assert "pyorbslam_amd/csrc/orbfe_fuse.hip" in (ROOT / "Makefile").read_text()
 
 
 OUTS = ("best_idx", "best_dist", "status")

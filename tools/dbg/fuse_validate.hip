@@ -1,8 +1,12 @@
-// fuse_validate.hip — host-side sanitizer check of orbfe_fuse_search's argument validation.
+// fuse_validate.hip — host-side sanitizer check of the argument validation of orbfe_fuse_search and
+// orbfe_scw_search.
 //
-// A program of its own: it links orbfe_fuse.hip alone and calls the entry only with arguments that the validation
+// A program of its own: it links orbfe_fuse.hip alone and calls the entries only with arguments that the validation
 // refuses (or with nothing to do), all of which return before any device call, so it runs on a machine without a
-// GPU.  Build and run with tools/dbg/fuse_validate_asan.sh (host code under -fsanitize=address,undefined).
+// GPU.  What orbfe_scw_search accepts where orbfe_fuse_search refuses (a null blocked, anything in slot 4 of the
+// keyframe scalars) would reach the device on its own, so each is paired with one later refusal and the message must
+// be that later one's.  Build and run with tools/dbg/fuse_validate_asan.sh (host code under
+// -fsanitize=address,undefined).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -26,7 +30,7 @@ struct Input {
     std::vector<int64_t> off = {0, 2}, cell_at = {0, 5}, idx_at = {0, 2}, lvl_off = {0, 2};
     std::vector<double> xy = {1.0, 1.0, 2.0, 2.0}, ur = {-1.0, 0.5}, scale = {1.0, 1.2}, is2 = {1.0, 0.7};
     std::vector<int32_t> octave = {0, 1}, cell_off = {0, 1, 1, 2, 2}, cell_idx = {0, 1};
-    std::vector<uint8_t> desc = std::vector<uint8_t>(64, 7), pdesc = std::vector<uint8_t>(64, 9);
+    std::vector<uint8_t> desc = std::vector<uint8_t>(64, 7), pdesc = std::vector<uint8_t>(64, 9), blocked = {0, 1};
     std::vector<double> pt = std::vector<double>(2 * ORBFE_FUSE_PT_F64, 1.0);
     std::vector<int32_t> bi = {-7, -7}, bd = {-7, -7};
     std::vector<uint8_t> st = {7, 7};
@@ -40,9 +44,18 @@ struct Input {
     const T* p(const std::vector<T>& v) const {
         return v.data() == skip ? nullptr : v.data();
     }
-    int run() {
-        orbfe_fuse_out o{bi.data() == skip ? nullptr : bi.data(), bd.data() == skip ? nullptr : bd.data(),
-                         st.data() == skip ? nullptr : st.data()};
+    template <class T>
+    T* p(std::vector<T>& v) {
+        return v.data() == skip ? nullptr : v.data();
+    }
+    int run(bool scw) {
+        if (scw) {  // no ur, no is2
+            orbfe_scw_out o{p(bi), p(bd), p(st)};
+            return orbfe_scw_search(p(kf), p(ki), p(off), p(xy), p(octave), p(desc), p(blocked), p(cell_at),
+                                    p(cell_off), p(idx_at), p(cell_idx), p(lvl_off), p(scale), n_kf, p(pt), p(pdesc),
+                                    n_pts, th, eps, null_out ? nullptr : &o, stride);
+        }
+        orbfe_fuse_out o{p(bi), p(bd), p(st)};
         return orbfe_fuse_search(p(kf), p(ki), p(off), p(xy), p(octave), p(ur), p(desc), p(cell_at), p(cell_off),
                                  p(idx_at), p(cell_idx), p(lvl_off), p(scale), p(is2), n_kf, p(pt), p(pdesc), n_pts, th,
                                  eps, null_out ? nullptr : &o, stride);
@@ -51,22 +64,23 @@ struct Input {
 };
 
 int failures = 0, checks = 0;
+bool scw = false;  // the entry under test
 
-void expect(const char* what, int want, const std::function<void(Input&)>& breakit) {
+// message: words the refusal's message must hold ("" for any)
+void expect(const char* what, int want, const std::function<void(Input&)>& breakit, const char* message = "") {
     Input in;
     breakit(in);
-    const int rc = in.run();
+    orbfe::g_err.clear();
+    const int rc = in.run(scw);
     ++checks;
-    if (rc != want || !in.untouched()) {
-        std::printf("FAIL %s: rc %d (want %d), outputs %s, message: %s\n", what, rc, want,
-                    in.untouched() ? "untouched" : "WRITTEN", orbfe::g_err.c_str());
+    if (rc != want || !in.untouched() || orbfe::g_err.find(message) == std::string::npos) {
+        std::printf("FAIL %s %s: rc %d (want %d), outputs %s, message: %s (want: %s)\n", scw ? "scw" : "fuse", what, rc,
+                    want, in.untouched() ? "untouched" : "WRITTEN", orbfe::g_err.c_str(), message);
         ++failures;
     }
 }
 
-}  // namespace
-
-int main() {
+void refusals() {
     const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
     const int E = ORBFE_EINVAL;
     expect("negative keyframe count", E, [](Input& i) { i.n_kf = -1; });
@@ -79,13 +93,12 @@ int main() {
     expect("no keyframes", ORBFE_OK, [](Input& i) { i.n_kf = 0; });
     expect("no points", ORBFE_OK, [](Input& i) { i.n_pts = 0; });
     expect("null out", E, [](Input& i) { i.null_out = true; });
-#define NULLARG(field) expect("null " #field, E, [](Input& i) { i.skip = i.field.data(); })
+#define NULLARG(field) expect("null " #field, E, [](Input& i) { i.skip = i.field.data(); }, "null argument")
     NULLARG(kf);
     NULLARG(ki);
     NULLARG(off);
     NULLARG(xy);
     NULLARG(octave);
-    NULLARG(ur);
     NULLARG(desc);
     NULLARG(cell_at);
     NULLARG(cell_off);
@@ -93,7 +106,6 @@ int main() {
     NULLARG(cell_idx);
     NULLARG(lvl_off);
     NULLARG(scale);
-    NULLARG(is2);
     NULLARG(pt);
     NULLARG(pdesc);
     NULLARG(bi);
@@ -107,7 +119,7 @@ int main() {
     expect("grid entries above the cap", E, [](Input& i) { i.idx_at[1] = ORBFE_BOW_MAX_FRAME + 1; });
     expect("level count 0", E, [](Input& i) { i.ki[2] = 0; });
     expect("level count negative", E, [](Input& i) { i.ki[2] = -5; });
-    expect("level tables of another length", E, [](Input& i) { i.ki[2] = 1; });
+    expect("level table of another length", E, [](Input& i) { i.ki[2] = 1; }, "one entry per level");
     expect("no grid columns", E, [](Input& i) { i.ki[0] = 0; });
     expect("huge grid", E, [](Input& i) { i.ki[1] = 1 << 30; });
     expect("grid offsets not columns * rows + 1", E, [](Input& i) { i.ki[0] = 3; });
@@ -119,18 +131,39 @@ int main() {
     expect("octave past the levels", E, [](Input& i) { i.octave[1] = 2; });
     expect("octave negative", E, [](Input& i) { i.octave[0] = -1; });
     for (int c = 0; c < ORBFE_FUSE_KF_F64; ++c) {
-        expect("keyframe scalar nan", E, [&](Input& i) { i.kf[c] = nan; });
-        expect("keyframe scalar inf", E, [&](Input& i) { i.kf[c] = -inf; });
+        if (scw && c == 4) continue;  // bf: not read, see below
+        expect("keyframe scalar nan", E, [&](Input& i) { i.kf[c] = nan; }, "a scalar is not finite");
+        expect("keyframe scalar inf", E, [&](Input& i) { i.kf[c] = -inf; }, "a scalar is not finite");
     }
     for (int c = 0; c < 2 * ORBFE_FUSE_PT_F64; ++c) expect("point scalar nan", E, [&](Input& i) { i.pt[c] = nan; });
     expect("coordinate inf", E, [&](Input& i) { i.xy[3] = inf; });
-    expect("right coordinate nan", E, [&](Input& i) { i.ur[0] = nan; });
     expect("scale nan", E, [&](Input& i) { i.scale[1] = nan; });
-    expect("inverse sigma inf", E, [&](Input& i) { i.is2[0] = inf; });
+    if (scw) {
+        // accepted by the validation: the refusal is the later one, of the point scalar
+        const char* later = "a point scalar is not finite";
+        expect("null blocked goes on", E, [&](Input& i) { i.skip = i.blocked.data(), i.pt[0] = nan; }, later);
+        expect("bf nan goes on", E, [&](Input& i) { i.kf[4] = nan, i.pt[0] = nan; }, later);
+        expect("bf inf goes on", E, [&](Input& i) { i.kf[4] = -inf, i.pt[0] = nan; }, later);
+    } else {
+        NULLARG(ur);
+        NULLARG(is2);
+        expect("right coordinate nan", E, [&](Input& i) { i.ur[0] = nan; });
+        expect("inverse sigma inf", E, [&](Input& i) { i.is2[0] = inf; });
+    }
     float ms = -1.f;
-    if (orbfe_fuse_search_last_ms(nullptr) != E || orbfe_fuse_search_last_ms(&ms) != ORBFE_OK || ms != 0.f) {
-        std::printf("FAIL last_ms\n");
+    const auto last_ms = scw ? orbfe_scw_search_last_ms : orbfe_fuse_search_last_ms;
+    if (last_ms(nullptr) != E || last_ms(&ms) != ORBFE_OK || ms != 0.f) {
+        std::printf("FAIL %s last_ms\n", scw ? "scw" : "fuse");
         ++failures;
+    }
+}
+
+}  // namespace
+
+int main() {
+    for (bool s : {false, true}) {
+        scw = s;
+        refusals();
     }
     std::printf("%d checks, %d failures\n", checks, failures);
     return failures ? 1 : 0;

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds tools/dbg/fuse_validate.hip with orbfe_fuse.hip, host code under AddressSanitizer and UBSan, and runs it on
-# the CPU: every call returns from the argument validation, before any device call.
+# the CPU: every call of orbfe_fuse_search and orbfe_scw_search returns from the argument validation, before any
+# device call.
 set -euo pipefail
 cd "$(dirname "$0")/../.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
