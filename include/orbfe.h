@@ -42,7 +42,8 @@ extern "C" {
                                * orbfe_fuse_search, orbfe_fuse_search_last_ms and orbfe_fuse_out, and
                                * orbfe_kfdb_query_many, orbfe_kfdb_query_many_device, orbfe_kfdb_set_scratch_limit,
                                * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out, and orbfe_scw_search,
-                               * orbfe_scw_search_last_ms and orbfe_scw_out */
+                               * orbfe_scw_search_last_ms and orbfe_scw_out, and orbfe_sim3_search,
+                               * orbfe_sim3_search_last_ms and orbfe_sim3_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -733,6 +734,57 @@ int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t*
                      double th, double eps, const orbfe_scw_out* out, int64_t out_stride);
 /* Kernel time of the last orbfe_scw_search (ms, HIP events), for measurement. */
 int orbfe_scw_search_last_ms(float* ms);
+
+/* ---- loop closing's mutual Sim3 search (ORBMatcher.search_by_sim3, ORBMatcher.py:713-848) ----
+ *
+ * k_sim3_search, one launch for n_srch searches.  A search is one direction of one keyframe pair (:742-789 or
+ * :791-838): a target keyframe, a pose in two stages, and a list of map points of its own.  The mutual check and the
+ * TH_HIGH test (:788, :840-846) stay with the caller.
+ * The keyframes are orbfe_scw_search's arrays without `blocked`; a keyframe that several searches target appears
+ * once.  Of a keyframe's ORBFE_FUSE_KF_F64 block only slots [20..26] are read (bounds, inverse cell sizes, log scale
+ * factor); slots [0..19] (intrinsics, bf, pose, centre) may hold anything.  The point table is orbfe_fuse_search's,
+ * ORBFE_FUSE_PT_F64 doubles and a descriptor per point; slots [3..5] (the normal) are not read and may hold anything,
+ * non-finite values included.
+ * Per search: ORBFE_SIM3_F64 doubles
+ *   [0..3] fx fy cx cy   [4..12] Rw row-major   [13..15] tw   [16..24] sR row-major   [25..27] t
+ * (the reference projects both directions with pKF1's intrinsics, so they belong to the search and not to the
+ * target; sR and t as the caller got them from the Sim3 with the reference's expressions, widened exactly), the
+ * index srch_kf[s] of its target keyframe, and items [srch_off[s], srch_off[s + 1]) of item_pt, each an index into
+ * the point table (repeats allowed, any order).
+ * Per item, in IEEE double in this operation order without contraction (sums of three from the left):
+ *   c1 = Rw p + tw; c = sR c1 + t; c.z < 0: no candidate.  invz = 1 / c.z (c.z == 0 gives inf, and u, v below fail
+ *   the image test); u = fx * (c.x * invz) + cx, v = fy * (c.y * invz) + cy with the search's intrinsics;
+ *   mnMinX <= u < mnMaxX and mnMinY <= v < mnMaxY of the target; dist = sqrt((c.x^2 + c.y^2) + c.z^2) in [min, max]
+ *   distance; there is no viewing gate; level = ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) clamped to
+ *   [0, levels - 1]; r = th * scale[level]; the cell window and the candidates are orbfe_scw_search's with nothing
+ *   blocked.
+ * Outputs at [i], i < srch_off[n_srch], flat over the items: best_idx (feature index of the target or -1),
+ * best_dist (Hamming distance or -1), status.  status gets ORBFE_FUSE_MARGINAL under orbfe_fuse_search's bounds
+ * scaled by eps, carried through both stages: each component of c1 has 4 eps times the sum of its terms'
+ * magnitudes, each component of c has sum_j |sR_ij| E1_j + 4 eps (sum_j |sR_ij c1_j| + |t_i|), and dist has the sum
+ * of the three component bounds besides its own rounding; also when an intermediate is not finite.  The limits are
+ * orbfe_fuse_search's.  A workgroup takes up to ORBFE_FUSE_CHUNK items of one search; an empty search launches
+ * nothing. */
+#define ORBFE_SIM3_F64 28
+typedef struct orbfe_sim3_out {
+    int32_t* best_idx;  /* one per item */
+    int32_t* best_dist; /* one per item */
+    uint8_t* status;    /* one per item */
+} orbfe_sim3_out;
+/* Host buffers, synchronous; the keyframe arrays and their checks are orbfe_scw_search's, except that slots [0..19]
+ * of a keyframe block are exempt from the finiteness check.  Also ORBFE_EINVAL, before any device call, for a
+ * srch_kf outside [0, n_kf), srch_off[0] != 0 or a srch_off that decreases, an item_pt outside [0, n_pts), a
+ * srch_f64 entry that is not finite, a point scalar outside slots [3..5] that is not finite.  n_srch == 0 or
+ * srch_off[n_srch] == 0 launches nothing and succeeds.  Process-wide buffers, stream and events of its own:
+ * concurrent callers take turns. */
+int orbfe_sim3_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                      const int32_t* octave, const uint8_t* desc32, const int64_t* cell_at, const int32_t* cell_off,
+                      const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off, const double* scale,
+                      int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                      const double* srch_f64, const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch,
+                      const int32_t* item_pt, double th, double eps, const orbfe_sim3_out* out);
+/* Kernel time of the last orbfe_sim3_search (ms, HIP events), for measurement. */
+int orbfe_sim3_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

@@ -71,6 +71,7 @@ class TriMatchOut(C.Structure):
 
 ORBFE_FUSE_MARGINAL = 1  # orbfe_fuse_search status: a decision of the item lies within rounding of its threshold
 ORBFE_FUSE_KF_F64, ORBFE_FUSE_PT_F64, ORBFE_FUSE_CHUNK = 27, 9, 256
+ORBFE_SIM3_F64 = 28  # doubles per search of orbfe_sim3_search
 
 
 class FuseOut(C.Structure):
@@ -80,6 +81,11 @@ class FuseOut(C.Structure):
 
 class ScwOut(C.Structure):
     """orbfe_scw_out: caller-owned output arrays of orbfe_scw_search."""
+    _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
+
+
+class Sim3Out(C.Structure):
+    """orbfe_sim3_out: caller-owned output arrays of orbfe_sim3_search, flat over the items."""
     _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
 
 
@@ -208,6 +214,10 @@ SIGNATURES = {
     "orbfe_scw_search": [C.c_void_p] * 13 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
                                              C.POINTER(ScwOut), C.c_int64],
     "orbfe_scw_search_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_sim3_search": [C.c_void_p] * 12 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double,
+                                              C.POINTER(Sim3Out)],
+    "orbfe_sim3_search_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -1,7 +1,8 @@
 // orbfe_fuse.hip — the search half of the reference's three projection searches, for every (keyframe, map point) of a
 // call in one launch on gfx950: ORBMatcher.fuse_pkf_mp (ORBMatcher.py:498-567) as k_fuse_search, and LoopClosing's two
 // Sim3 searches, ORBMatcher.fuse_kf_scw_mp (:395-480) and ORBMatcher.search_by_projection_ckf_scw_mp (:850-922), as
-// k_scw_search.  Both kernels are instantiations of one body, proj_search<kScw>.
+// k_scw_search; and the two directions of ORBMatcher.search_by_sim3 (:713-848) for many keyframe pairs as
+// k_sim3_search.  All three kernels are instantiations of one body, proj_search<kMode>.
 //
 // The reference projects each map point into a keyframe, gates it (depth sign, image bounds, scale-invariance
 // distances, viewing angle), predicts its pyramid level, searches the keyframe's grid in a window of radius
@@ -11,7 +12,7 @@
 // dist < bestDist.  None of this reads what a fusion changes, so it runs here for all items at once and the caller
 // applies the matches afterwards in the reference's order.
 //
-// What the two variants do not share:
+// What the three variants do not share:
 //   k_fuse_search  also projects the right coordinate ur = u - bf / z and filters the candidates by a chi-square on
 //                  the reprojection error (three terms against 7.8 for a stereo feature, two against 5.99 for a mono
 //                  one).
@@ -20,6 +21,15 @@
 //                  expressions); and it has one more input: a byte per feature that takes the feature out of the
 //                  candidates (the ckf search skips a feature whose vpMatched slot is taken).  A blocked entry is
 //                  skipped first: it decides nothing, so it marks nothing either.
+//
+//   k_sim3_search  is k_scw_search without the blocked byte and without the viewing gate (the normal is not read), and
+//                  it reads nothing of the target's block before the bounds: the camera coordinates come in two
+//                  stages with a rounding in between, c1 = Rw p + tw and c = sR c1 + t, from the search's own
+//                  scalars; the intrinsics are the search's too (the reference projects both directions with
+//                  pKF1's); and the distance that is gated and that predicts the level is |c| in the target camera,
+//                  so the Sim3's scale moves the level.  Its launch is ragged: a search is a target, a pose and a
+//                  list of rows of the shared point table, and a 1-D grid runs over a host-built table of (search,
+//                  first item) chunks, so no workgroup straddles two searches and an empty search launches nothing.
 //
 // The depth gate: fuse_pkf_mp and fuse_kf_scw_mp skip z < 0, the ckf search z <= 0.  At z == 0 the first two run on to
 // 1 / 0, u and v become inf or NaN and fail the image test, so all three skip the point and one code path serves them.
@@ -60,6 +70,7 @@ constexpr int kPsGroup = 16;                // lanes that share one point's cand
 constexpr unsigned kPsNone = 0xFFFFFFFFu;
 constexpr int kPsKfF64 = ORBFE_FUSE_KF_F64;
 constexpr int kPsPtF64 = ORBFE_FUSE_PT_F64;
+constexpr int kPsSim3F64 = ORBFE_SIM3_F64;
 
 struct PsKfs {
     const double* f64;   // kPsKfF64 per keyframe
@@ -81,23 +92,48 @@ struct PsPts {
 struct PsOut {
     int32_t *best_idx, *best_dist;
     uint8_t* status;
-    int64_t stride;
+    int64_t stride;  // k_sim3_search: not read, the outputs are flat over the items
 };
+
+// k_sim3_search only: the searches, their items and the launch's chunk table
+struct PsSim3 {
+    const double* f64;       // kPsSim3F64 per search
+    const int32_t* kf;       // target keyframe per search
+    const int64_t* off;      // search s owns items [off[s], off[s + 1])
+    const int32_t* item_pt;  // point table row per item
+    const int64_t* chunk;    // (search, first item) per workgroup
+};
+
+enum PsMode { kPsFuse, kPsScw, kPsSim3 };
 
 // every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
 // is this one exactly
 __device__ __forceinline__ bool near_int(double a, double e) { return fabs(a - rint(a)) < e; }
 
-template <bool kScw>
+template <PsMode kMode>
 __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, double th, double eps,
-                                            const PsOut& out) {
+                                            const PsOut& out, [[maybe_unused]] const PsSim3& sx) {
+    constexpr bool kFuse = kMode == kPsFuse, kScw = kMode == kPsScw, kSim3 = kMode == kPsSim3;
     __shared__ double s_u[kPsChunk], s_v[kPsChunk], s_eu[kPsChunk], s_ev[kPsChunk], s_r[kPsChunk];
     __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, in k_fuse_search only
     __shared__ int16_t s_x0[kPsChunk], s_x1[kPsChunk], s_y0[kPsChunk], s_y1[kPsChunk], s_lvl[kPsChunk];
     __shared__ uint8_t s_st[kPsChunk];
-    const int k = blockIdx.y;
     const int tid = threadIdx.x;
-    const int64_t first = (int64_t)blockIdx.x * kPsChunk;
+    // the workgroup's keyframe, its first item and the end of its item range: (keyframe, chunk of the shared
+    // points) of a 2-D grid, or in k_sim3_search the chunk table's (search, first item) and the search's target
+    [[maybe_unused]] int srch = 0;
+    int k;
+    int64_t first, n_end;
+    if constexpr (kSim3) {
+        srch = (int)sx.chunk[2 * (int64_t)blockIdx.x];
+        first = sx.chunk[2 * (int64_t)blockIdx.x + 1];
+        n_end = sx.off[srch + 1];
+        k = sx.kf[srch];
+    } else {
+        k = blockIdx.y;
+        first = (int64_t)blockIdx.x * kPsChunk;
+        n_end = pt.n;
+    }
     const double* K = kf.f64 + (int64_t)k * kPsKfF64;
     const int cols = kf.i32[3 * k], rows = kf.i32[3 * k + 1], levels = kf.i32[3 * k + 2];
     const double* scale = kf.scale + kf.lvl_off[k];
@@ -108,20 +144,57 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
         double u = 0.0, v = 0.0, Eu = 0.0, Ev = 0.0, r = 0.0;
         [[maybe_unused]] double ur = 0.0, Eur = 0.0;
         const int64_t i = first + tid;
-        if (i < pt.n) {
-            const double* P = pt.f64 + i * kPsPtF64;
-            const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-            [[maybe_unused]] const double bf = kScw ? 0.0 : K[4];  // k_scw_search does not read the slot
+        if (i < n_end) {
+            const double* P;
+            if constexpr (kSim3)
+                P = pt.f64 + (int64_t)sx.item_pt[i] * kPsPtF64;
+            else
+                P = pt.f64 + i * kPsPtF64;
+            // k_sim3_search: the intrinsics are the search's (pKF1's in both directions), not the target's
+            [[maybe_unused]] const double* S = nullptr;
+            if constexpr (kSim3) S = sx.f64 + (int64_t)srch * kPsSim3F64;
+            const double* I = kSim3 ? S : K;
+            const double fx = I[0], fy = I[1], cx = I[2], cy = I[3];
+            [[maybe_unused]] const double bf = kFuse ? K[4] : 0.0;  // only k_fuse_search reads the slot
             const double minX = K[20], maxX = K[21], minY = K[22], maxY = K[23], winv = K[24], hinv = K[25],
                          lsf = K[26];
             const double p0 = P[0], p1 = P[1], p2 = P[2];
-            const double xc = ((K[5] * p0 + K[6] * p1) + K[7] * p2) + K[14];
-            const double yc = ((K[8] * p0 + K[9] * p1) + K[10] * p2) + K[15];
-            const double zc = ((K[11] * p0 + K[12] * p1) + K[13] * p2) + K[16];
-            const double Ex = 4.0 * eps * (((fabs(K[5] * p0) + fabs(K[6] * p1)) + fabs(K[7] * p2)) + fabs(K[14]));
-            const double Ey = 4.0 * eps * (((fabs(K[8] * p0) + fabs(K[9] * p1)) + fabs(K[10] * p2)) + fabs(K[15]));
-            const double Ez = 4.0 * eps * (((fabs(K[11] * p0) + fabs(K[12] * p1)) + fabs(K[13] * p2)) + fabs(K[16]));
+            double xc, yc, zc, Ex, Ey, Ez;
+            if constexpr (kSim3) {
+                // two stages with a rounding in between, as the reference: c1 = Rw p + tw, then c = sR c1 + t
+                const double *Rw = S + 4, *tw = S + 13, *sR = S + 16, *t = S + 25;
+                const double c0 = ((Rw[0] * p0 + Rw[1] * p1) + Rw[2] * p2) + tw[0];
+                const double c1 = ((Rw[3] * p0 + Rw[4] * p1) + Rw[5] * p2) + tw[1];
+                const double c2 = ((Rw[6] * p0 + Rw[7] * p1) + Rw[8] * p2) + tw[2];
+                const double E0 = 4.0 * eps * (((fabs(Rw[0] * p0) + fabs(Rw[1] * p1)) + fabs(Rw[2] * p2)) + fabs(tw[0]));
+                const double E1 = 4.0 * eps * (((fabs(Rw[3] * p0) + fabs(Rw[4] * p1)) + fabs(Rw[5] * p2)) + fabs(tw[1]));
+                const double E2 = 4.0 * eps * (((fabs(Rw[6] * p0) + fabs(Rw[7] * p1)) + fabs(Rw[8] * p2)) + fabs(tw[2]));
+                xc = ((sR[0] * c0 + sR[1] * c1) + sR[2] * c2) + t[0];
+                yc = ((sR[3] * c0 + sR[4] * c1) + sR[5] * c2) + t[1];
+                zc = ((sR[6] * c0 + sR[7] * c1) + sR[8] * c2) + t[2];
+                Ex = ((fabs(sR[0]) * E0 + fabs(sR[1]) * E1) + fabs(sR[2]) * E2) +
+                     4.0 * eps * (((fabs(sR[0] * c0) + fabs(sR[1] * c1)) + fabs(sR[2] * c2)) + fabs(t[0]));
+                Ey = ((fabs(sR[3]) * E0 + fabs(sR[4]) * E1) + fabs(sR[5]) * E2) +
+                     4.0 * eps * (((fabs(sR[3] * c0) + fabs(sR[4] * c1)) + fabs(sR[5] * c2)) + fabs(t[1]));
+                Ez = ((fabs(sR[6]) * E0 + fabs(sR[7]) * E1) + fabs(sR[8]) * E2) +
+                     4.0 * eps * (((fabs(sR[6] * c0) + fabs(sR[7] * c1)) + fabs(sR[8] * c2)) + fabs(t[2]));
+            } else {
+                xc = ((K[5] * p0 + K[6] * p1) + K[7] * p2) + K[14];
+                yc = ((K[8] * p0 + K[9] * p1) + K[10] * p2) + K[15];
+                zc = ((K[11] * p0 + K[12] * p1) + K[13] * p2) + K[16];
+                Ex = 4.0 * eps * (((fabs(K[5] * p0) + fabs(K[6] * p1)) + fabs(K[7] * p2)) + fabs(K[14]));
+                Ey = 4.0 * eps * (((fabs(K[8] * p0) + fabs(K[9] * p1)) + fabs(K[10] * p2)) + fabs(K[15]));
+                Ez = 4.0 * eps * (((fabs(K[11] * p0) + fabs(K[12] * p1)) + fabs(K[13] * p2)) + fabs(K[16]));
+            }
             do {
+                if constexpr (kSim3) {
+                    // the camera coordinates are themselves rounded products of finite inputs: an overflow in
+                    // either stage decides nothing
+                    if (!isfinite(((xc + yc) + zc) + ((Ex + Ey) + Ez))) {
+                        st = ORBFE_FUSE_MARGINAL;
+                        break;
+                    }
+                }
                 if (zc < 0.0) {
                     if (-zc < Ez) st = ORBFE_FUSE_MARGINAL;
                     break;
@@ -134,7 +207,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 u = fxx + cx;
                 v = fyy + cy;
                 [[maybe_unused]] double bz = 0.0;
-                if constexpr (!kScw) {
+                if constexpr (kFuse) {
                     bz = bf * iz;
                     ur = u - bz;
                 }
@@ -150,7 +223,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 Eu = fabs(fx) * Exn + 4.0 * eps * Mu;
                 Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
                 double sum;  // finite when everything phase 2 reads is
-                if constexpr (kScw) {
+                if constexpr (!kFuse) {
                     sum = ((u + v) + Eu) + Ev;
                 } else {
                     Eur = (Eu + fabs(bf) * Eiz) + 4.0 * eps * (fabs(bz) + Mu);
@@ -164,9 +237,21 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     fabs(v - minY) < Ev + eps * fabs(minY) || fabs(v - maxY) < Ev + eps * fabs(maxY))
                     st = ORBFE_FUSE_MARGINAL;
                 if (!in) break;
-                const double po0 = p0 - K[17], po1 = p1 - K[18], po2 = p2 - K[19];
-                const double dist = sqrt((po0 * po0 + po1 * po1) + po2 * po2);
-                const double Ed = 6.0 * eps * dist;
+                [[maybe_unused]] double po0 = 0.0, po1 = 0.0, po2 = 0.0;
+                double dist, Ed;
+                if constexpr (kSim3) {
+                    // the norm of the target camera's coordinates, so the Sim3's scale moves the level.  Its
+                    // operands are rounded sums of unknown cancellation: the norm moves by at most the length of
+                    // what moves them
+                    dist = sqrt((xc * xc + yc * yc) + zc * zc);
+                    Ed = ((Ex + Ey) + Ez) + 6.0 * eps * dist;
+                } else {
+                    po0 = p0 - K[17];
+                    po1 = p1 - K[18];
+                    po2 = p2 - K[19];
+                    dist = sqrt((po0 * po0 + po1 * po1) + po2 * po2);
+                    Ed = 6.0 * eps * dist;
+                }
                 const double minD = P[6], maxD = P[7];
                 if (!isfinite(dist)) {
                     st = ORBFE_FUSE_MARGINAL;
@@ -175,17 +260,27 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 if (fabs(dist - minD) < Ed + eps * fabs(minD) || fabs(dist - maxD) < Ed + eps * fabs(maxD))
                     st = ORBFE_FUSE_MARGINAL;
                 if (dist < minD || dist > maxD) break;
-                const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
-                const double dot = (t0 + t1) + t2;
-                const double half = 0.5 * dist;
-                if (fabs(dot - half) < 5.0 * eps * ((fabs(t0) + fabs(t1)) + fabs(t2)) + Ed) st = ORBFE_FUSE_MARGINAL;
-                if (dot < half) break;
+                if constexpr (!kSim3) {  // search_by_sim3 has no viewing gate, and does not read the normal
+                    const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
+                    const double dot = (t0 + t1) + t2;
+                    const double half = 0.5 * dist;
+                    if (fabs(dot - half) < 5.0 * eps * ((fabs(t0) + fabs(t1)) + fabs(t2)) + Ed)
+                        st = ORBFE_FUSE_MARGINAL;
+                    if (dot < half) break;
+                }
                 const double q = log(P[8] / dist) / lsf;
                 if (!isfinite(q)) {
                     st = ORBFE_FUSE_MARGINAL;
                     break;
                 }
-                if (near_int(q, 10.0 * eps / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
+                if constexpr (kSim3) {
+                    // dist is off by up to rd of itself, and |log(1 - rd)| <= 1.5 rd for rd <= 0.25
+                    const double rd = Ed / dist;
+                    if (!(rd <= 0.25)) st = ORBFE_FUSE_MARGINAL;
+                    if (near_int(q, (1.5 * rd + 4.0 * eps) / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
+                } else {
+                    if (near_int(q, 10.0 * eps / fabs(lsf) + 4.0 * eps * fabs(q))) st = ORBFE_FUSE_MARGINAL;
+                }
                 const double cq = ceil(q);
                 const int level = cq < 0.0 ? 0 : (cq > (double)(levels - 1) ? levels - 1 : (int)cq);
                 r = th * scale[level];
@@ -213,7 +308,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
         s_v[tid] = v;
         s_eu[tid] = Eu;
         s_ev[tid] = Ev;
-        if constexpr (!kScw) {
+        if constexpr (kFuse) {
             s_ur[tid] = ur;
             s_eur[tid] = Eur;
         }
@@ -238,25 +333,29 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
     [[maybe_unused]] const uint8_t* blk = nullptr;
     if constexpr (kScw) {
         blk = kf.blocked ? kf.blocked + base : nullptr;
-    } else {
+    } else if constexpr (kFuse) {
         uright = kf.u_right + base;
         is2 = kf.inv_sigma2 + kf.lvl_off[k];
     }
     for (int j = g; j < kPsChunk; j += kPsChunk / kPsGroup) {
         const int64_t i = first + j;
-        if (i >= pt.n) break;
+        if (i >= n_end) break;
         const int level = s_lvl[j];
         unsigned st = s_st[j];
         unsigned key = kPsNone;
         if (level >= 0) {
             const double u = s_u[j], v = s_v[j], Eu = s_eu[j], Ev = s_ev[j], r = s_r[j];
             [[maybe_unused]] double ur = 0.0, Eur = 0.0;
-            if constexpr (!kScw) {
+            if constexpr (kFuse) {
                 ur = s_ur[j];
                 Eur = s_eur[j];
             }
             const int x0 = s_x0[j], x1 = s_x1[j], y0 = s_y0[j], y1 = s_y1[j];
-            const uint4* pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
+            const uint4* pd;
+            if constexpr (kSim3)
+                pd = reinterpret_cast<const uint4*>(pt.desc + (int64_t)sx.item_pt[i] * 32);
+            else
+                pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
             const uint4 qa = pd[0], qb = pd[1];
             const double er_r = eps * fabs(r);
             for (int ix = x0; ix <= x1; ++ix) {
@@ -272,7 +371,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     if (!(fabs(dx) < r && fabs(dy) < r)) continue;
                     const int o = oct[f];
                     if (o < level - 1 || o > level) continue;
-                    if constexpr (!kScw) {
+                    if constexpr (kFuse) {
                         const double kr = uright[f];
                         const double ex = u - kx, ey = v - ky;
                         const double bxy = (2.0 * fabs(ex) * Edx + Edx * Edx) + (2.0 * fabs(ey) * Edy + Edy * Edy);
@@ -307,7 +406,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
             }
         }
         if (l == 0) {
-            const int64_t at = (int64_t)k * out.stride + i;
+            const int64_t at = kSim3 ? i : (int64_t)k * out.stride + i;
             out.best_idx[at] = key == kPsNone ? -1 : cidx[key & 0xFFFFu];
             out.best_dist[at] = key == kPsNone ? -1 : (int)(key >> 16);
             out.status[at] = (uint8_t)st;
@@ -316,11 +415,17 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
 }
 
 __global__ __launch_bounds__(kPsChunk) void k_fuse_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out) {
-    proj_search<false>(kf, pt, th, eps, out);
+    proj_search<kPsFuse>(kf, pt, th, eps, out, PsSim3{});
 }
 
 __global__ __launch_bounds__(kPsChunk) void k_scw_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out) {
-    proj_search<true>(kf, pt, th, eps, out);
+    proj_search<kPsScw>(kf, pt, th, eps, out, PsSim3{});
+}
+
+// a 1-D grid over the chunk table: a workgroup is up to kPsChunk items of one search
+__global__ __launch_bounds__(kPsChunk) void k_sim3_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out,
+                                                          PsSim3 sx) {
+    proj_search<kPsSim3>(kf, pt, th, eps, out, sx);
 }
 
 }  // namespace orbfe
@@ -329,20 +434,21 @@ namespace {
 
 // scratch of one entry: process-wide, created on first use and never torn down (the HIP runtime may already be gone
 // when static destructors run); callers of that entry on several threads take turns.  Each entry has an instance of
-// its own, so the two do not wait for each other and each last_ms is its own entry's.
+// its own, so the three do not wait for each other and each last_ms is its own entry's.
 struct Searcher {
     std::mutex mu;
     DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, blocked bytes, status
-    DevBuf<double> d_f64;   // keyframe scalars, xy, u_right, scale, inv_sigma2, point scalars
-    DevBuf<int64_t> d_i64;  // off, cell_at, idx_at, lvl_off
-    DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, best_idx, best_dist
+    DevBuf<double> d_f64;   // keyframe scalars, xy, u_right, scale, inv_sigma2, point scalars, search scalars
+    DevBuf<int64_t> d_i64;  // off, cell_at, idx_at, lvl_off, srch_off, chunk table
+    DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, srch_kf, item_pt, best_idx, best_dist
     std::vector<int32_t> h_i32;
     std::vector<uint8_t> h_st;
+    std::vector<int64_t> h_chunk;  // k_sim3_search: (search, first item) per workgroup
     hipStream_t stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.f;
 };
-template <bool kScw>
+template <PsMode kMode>
 Searcher& searcher() {
     static Searcher* m = new Searcher;
     return *m;
@@ -358,24 +464,60 @@ bool all_finite(const double* v, int64_t n) {
 
 size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// Both entries: validate, stage, launch, download.  kScw: u_right and inv_sigma2 are not looked at, slot 4 of a
-// keyframe's scalars may hold anything, and blocked may be null (nothing is blocked).  Otherwise blocked is not
-// looked at.  Out is the entry's orbfe_*_out.
-template <bool kScw, class Out>
+// what orbfe_sim3_search has besides the keyframes and the point table
+struct Sim3In {
+    const double* f64;
+    const int32_t* kf;
+    const int64_t* off;
+    int32_t n;
+    const int32_t* item_pt;
+};
+
+// All three entries: validate, stage, launch, download.  Not kPsFuse: u_right and inv_sigma2 are not looked at and
+// slot 4 of a keyframe's scalars may hold anything.  kPsScw: blocked may be null (nothing is blocked); otherwise
+// blocked is not looked at.  kPsSim3: sx is the searches, slots 0-19 of a keyframe's scalars and 3-5 of a point's may
+// hold anything, out_stride is not looked at and the outputs are flat over the items.  Out is the entry's
+// orbfe_*_out.
+template <PsMode kMode, class Out>
 void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy, const int32_t* octave,
             const double* u_right, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
             const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
             const double* scale, const double* inv_sigma2, int32_t n_kf, const double* pt_f64,
-            const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride) {
+            const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride,
+            [[maybe_unused]] const Sim3In* sx = nullptr) {
+    constexpr bool kFuse = kMode == kPsFuse, kScw = kMode != kPsFuse, kSim3 = kMode == kPsSim3;
     if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
     if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
     if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
         throw Error(ORBFE_EINVAL, "th and eps must be finite and eps not negative");
-    if (n_kf == 0 || n_pts == 0) return;
+    int64_t n_items = 0;
+    if constexpr (kSim3) {
+        if (sx->n < 0) throw Error(ORBFE_EINVAL, "bad argument");
+        if (sx->n == 0) return;
+        if (!sx->off) throw Error(ORBFE_EINVAL, "null argument");
+        if (sx->off[0] != 0) throw Error(ORBFE_EINVAL, "srch_off[0] must be 0");
+        for (int32_t q = 0; q < sx->n; ++q)
+            if (sx->off[q + 1] < sx->off[q])
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": srch_off must not decrease");
+        n_items = sx->off[sx->n];
+        if (n_items == 0) return;
+        if (!sx->f64 || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
+        for (int32_t q = 0; q < sx->n; ++q) {
+            if (sx->kf[q] < 0 || sx->kf[q] >= n_kf)
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the target is outside the keyframes");
+            if (!all_finite(sx->f64 + (int64_t)q * ORBFE_SIM3_F64, ORBFE_SIM3_F64))
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": a scalar is not finite");
+        }
+        for (int64_t i = 0; i < n_items; ++i)
+            if (sx->item_pt[i] < 0 || sx->item_pt[i] >= n_pts)
+                throw Error(ORBFE_EINVAL, "an item is outside the point table");
+    } else {
+        if (n_kf == 0 || n_pts == 0) return;
+    }
     if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale ||
         (!kScw && !inv_sigma2) || !pt_f64 || !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
         throw Error(ORBFE_EINVAL, "null argument");
-    if (out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
+    if (!kSim3 && out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
     if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
         throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
     for (int32_t k = 0; k < n_kf; ++k)
@@ -388,9 +530,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
         if (n > ORBFE_BOW_MAX_FRAME || ni > ORBFE_BOW_MAX_FRAME)
             throw Error(ORBFE_EINVAL, at_kf(k, "more features or grid entries than the limit of " +
                                                    std::to_string(ORBFE_BOW_MAX_FRAME) + " per keyframe"));
-        // slot 4 is bf, which k_scw_search does not read
+        // slot 4 is bf, which only k_fuse_search reads; k_sim3_search reads none of the slots before the bounds
         const double* Kk = kf_f64 + (int64_t)k * ORBFE_FUSE_KF_F64;
-        if (!(all_finite(Kk, 4) && (kScw || std::isfinite(Kk[4])) && all_finite(Kk + 5, ORBFE_FUSE_KF_F64 - 5)))
+        if (!((kSim3 || (all_finite(Kk, 4) && (kScw || std::isfinite(Kk[4])) && all_finite(Kk + 5, 15))) &&
+              all_finite(Kk + 20, ORBFE_FUSE_KF_F64 - 20)))
             throw Error(ORBFE_EINVAL, at_kf(k, "a scalar is not finite"));
         const int64_t cols = kf_i32[3 * k], rows = kf_i32[3 * k + 1], levels = kf_i32[3 * k + 2];
         if (levels <= 0) throw Error(ORBFE_EINVAL, at_kf(k, "the level count must be positive"));
@@ -418,24 +561,45 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
         }
     }
-    if (!all_finite(pt_f64, n_pts * ORBFE_FUSE_PT_F64)) throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+    if constexpr (kSim3) {
+        for (int64_t i = 0; i < n_pts; ++i)  // slots 3-5, the normal, are not read
+            if (!(all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64, 3) && all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64 + 6, 3)))
+                throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+    } else {
+        if (!all_finite(pt_f64, n_pts * ORBFE_FUSE_PT_F64)) throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+    }
+    // the outputs: a row of out_stride per keyframe, or flat over the items
     const size_t nk = (size_t)n_kf, np = (size_t)n_pts, os = (size_t)out_stride;
+    const size_t n_out = kSim3 ? (size_t)n_items : nk * os;
+    [[maybe_unused]] size_t ns = 0, n_chunk = 0;
     const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
                  nl = (size_t)lvl_off[n_kf];
     // what only one variant stages has no room in the other's buffers
-    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kScw ? pad16(n) : 0;
-    const bool has_blocked = kScw && blocked != nullptr && n > 0;
-    Searcher& m = searcher<kScw>();
+    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kMode == kPsScw ? pad16(n) : 0;
+    const bool has_blocked = kMode == kPsScw && blocked != nullptr && n > 0;
+    Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
+    if constexpr (kSim3) {
+        // no workgroup straddles two searches, and an empty search gets none
+        ns = (size_t)sx->n;
+        m.h_chunk.clear();
+        for (int32_t q = 0; q < sx->n; ++q)
+            for (int64_t i = sx->off[q]; i < sx->off[q + 1]; i += kPsChunk) {
+                m.h_chunk.push_back(q);
+                m.h_chunk.push_back(i);
+            }
+        n_chunk = m.h_chunk.size() / 2;
+        if (n_chunk > 0x7FFFFFFFu) throw Error(ORBFE_EINVAL, "more items than one launch takes");
+    }
     if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
     for (hipEvent_t& e : m.ev)
         if (!e) HIPCK(hipEventCreate(&e));
     hipStream_t s = m.stream;
     // descriptors are read as uint4: both blocks start on 16 bytes
-    m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + n_blk + nk * os);
-    m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64);
-    m.d_i64.ensure(4 * (nk + 1));
-    m.d_i32.ensure(3 * nk + n + nc + ni + 2 * nk * os);
+    m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + n_blk + n_out);
+    m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 + ns * ORBFE_SIM3_F64);
+    m.d_i64.ensure(4 * (nk + 1) + (kSim3 ? ns + 1 + 2 * n_chunk : 0));
+    m.d_i32.ensure(3 * nk + n + nc + ni + (kSim3 ? ns + n_out : 0) + 2 * n_out);
     uint8_t* d_desc = m.d_u8.p;
     uint8_t* d_pdesc = d_desc + pad16(n * 32);
     uint8_t* d_blk = d_pdesc + pad16(np * 32);
@@ -446,16 +610,21 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     double* d_scale = d_ur + n_ur;
     double* d_is2 = d_scale + nl;
     double* d_pt = d_is2 + n_is2;
+    [[maybe_unused]] double* d_sx = d_pt + np * ORBFE_FUSE_PT_F64;
     int64_t* d_off = m.d_i64.p;
     int64_t* d_cat = d_off + nk + 1;
     int64_t* d_iat = d_cat + nk + 1;
     int64_t* d_lvl = d_iat + nk + 1;
+    [[maybe_unused]] int64_t* d_soff = d_lvl + nk + 1;
+    [[maybe_unused]] int64_t* d_chunk = d_soff + ns + 1;
     int32_t* d_ki = m.d_i32.p;
     int32_t* d_oct = d_ki + 3 * nk;
     int32_t* d_coff = d_oct + n;
     int32_t* d_cidx = d_coff + nc;
-    int32_t* d_bi = d_cidx + ni;
-    int32_t* d_bd = d_bi + nk * os;
+    [[maybe_unused]] int32_t* d_skf = d_cidx + ni;
+    [[maybe_unused]] int32_t* d_item = d_skf + ns;
+    int32_t* d_bi = kSim3 ? d_item + n_out : d_cidx + ni;
+    int32_t* d_bd = d_bi + n_out;
     auto up = [&](void* dst, const void* src, size_t bytes) {
         if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
     };
@@ -476,6 +645,15 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     up(d_oct, octave, n * sizeof(int32_t));
     up(d_coff, cell_off, nc * sizeof(int32_t));
     up(d_cidx, cell_idx, ni * sizeof(int32_t));
+    [[maybe_unused]] PsSim3 dsx{};
+    if constexpr (kSim3) {
+        up(d_sx, sx->f64, ns * ORBFE_SIM3_F64 * sizeof(double));
+        up(d_soff, sx->off, (ns + 1) * sizeof(int64_t));
+        up(d_chunk, m.h_chunk.data(), 2 * n_chunk * sizeof(int64_t));
+        up(d_skf, sx->kf, ns * sizeof(int32_t));
+        up(d_item, sx->item_pt, n_out * sizeof(int32_t));
+        dsx = PsSim3{d_sx, d_skf, d_soff, d_item, d_chunk};
+    }
     PsKfs kf{};
     kf.f64 = d_kf;
     kf.i32 = d_ki;
@@ -494,20 +672,30 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     kf.blocked = has_blocked ? d_blk : nullptr;
     const PsPts pt{d_pt, d_pdesc, n_pts};
     const PsOut d{d_bi, d_bd, d_st, out_stride};
-    const unsigned chunks = (unsigned)((np + kPsChunk - 1) / kPsChunk);
     HIPCK(hipEventRecord(m.ev[0], s));
-    constexpr auto kernel = kScw ? k_scw_search : k_fuse_search;
-    hipLaunchKernelGGL(kernel, dim3(chunks, (unsigned)n_kf), dim3(kPsChunk), 0, s, kf, pt, th, eps, d);
+    if constexpr (kSim3) {
+        hipLaunchKernelGGL(k_sim3_search, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx);
+    } else {
+        const unsigned chunks = (unsigned)((np + kPsChunk - 1) / kPsChunk);
+        constexpr auto kernel = kFuse ? k_fuse_search : k_scw_search;
+        hipLaunchKernelGGL(kernel, dim3(chunks, (unsigned)n_kf), dim3(kPsChunk), 0, s, kf, pt, th, eps, d);
+    }
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(m.ev[1], s));
     // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
     // the caller's arrays
-    m.h_i32.resize(2 * nk * os);
-    m.h_st.resize(nk * os);
-    HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * nk * os * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, nk * os, hipMemcpyDeviceToHost, s));
+    m.h_i32.resize(2 * n_out);
+    m.h_st.resize(n_out);
+    HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, n_out, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+    if constexpr (kSim3) {  // every item was written
+        std::memcpy(out->best_idx, m.h_i32.data(), n_out * sizeof(int32_t));
+        std::memcpy(out->best_dist, m.h_i32.data() + n_out, n_out * sizeof(int32_t));
+        std::memcpy(out->status, m.h_st.data(), n_out);
+        return;
+    }
     for (size_t k = 0; k < nk; ++k) {
         std::memcpy(out->best_idx + k * os, &m.h_i32[k * os], np * sizeof(int32_t));
         std::memcpy(out->best_dist + k * os, &m.h_i32[nk * os + k * os], np * sizeof(int32_t));
@@ -515,10 +703,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     }
 }
 
-template <bool kScw>
+template <PsMode kMode>
 void last_ms(float* ms) {
     if (!ms) throw Error(ORBFE_EINVAL, "null argument");
-    Searcher& m = searcher<kScw>();
+    Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
     *ms = m.last_ms;
 }
@@ -534,13 +722,13 @@ int orbfe_fuse_search(const double* kf_f64, const int32_t* kf_i32, const int64_t
                       const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const orbfe_fuse_out* out,
                       int64_t out_stride) {
     return guarded([&] {
-        search<false>(kf_f64, kf_i32, off, xy, octave, u_right, desc32, nullptr, cell_at, cell_off, idx_at, cell_idx,
+        search<kPsFuse>(kf_f64, kf_i32, off, xy, octave, u_right, desc32, nullptr, cell_at, cell_off, idx_at, cell_idx,
                       lvl_off, scale, inv_sigma2, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, out_stride);
     });
 }
 
 int orbfe_fuse_search_last_ms(float* ms) {
-    return guarded([&] { last_ms<false>(ms); });
+    return guarded([&] { last_ms<kPsFuse>(ms); });
 }
 
 int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
@@ -549,13 +737,30 @@ int orbfe_scw_search(const double* kf_f64, const int32_t* kf_i32, const int64_t*
                      const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
                      double th, double eps, const orbfe_scw_out* out, int64_t out_stride) {
     return guarded([&] {
-        search<true>(kf_f64, kf_i32, off, xy, octave, nullptr, desc32, blocked, cell_at, cell_off, idx_at, cell_idx,
+        search<kPsScw>(kf_f64, kf_i32, off, xy, octave, nullptr, desc32, blocked, cell_at, cell_off, idx_at, cell_idx,
                      lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, out_stride);
     });
 }
 
 int orbfe_scw_search_last_ms(float* ms) {
-    return guarded([&] { last_ms<true>(ms); });
+    return guarded([&] { last_ms<kPsScw>(ms); });
+}
+
+int orbfe_sim3_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                      const int32_t* octave, const uint8_t* desc32, const int64_t* cell_at, const int32_t* cell_off,
+                      const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off, const double* scale,
+                      int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                      const double* srch_f64, const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch,
+                      const int32_t* item_pt, double th, double eps, const orbfe_sim3_out* out) {
+    return guarded([&] {
+        const Sim3In sx{srch_f64, srch_kf, srch_off, n_srch, item_pt};
+        search<kPsSim3>(kf_f64, kf_i32, off, xy, octave, nullptr, desc32, nullptr, cell_at, cell_off, idx_at, cell_idx,
+                        lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, 0, &sx);
+    });
+}
+
+int orbfe_sim3_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<kPsSim3>(ms); });
 }
 
 }  // extern "C"

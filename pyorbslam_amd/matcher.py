@@ -32,7 +32,9 @@ search_for_triangulation_many (k_tri_match).  Each returns what the loop of sing
 the kernels' arrays cannot express, or whose float64 decision lies within rounding of its threshold, takes the
 single search.  fuse_pkf_mp_many (k_fuse_search) does the same for LocalMapping's fusion loops: one launch for
 the search of every (keyframe, point), then the matches applied on the host in the reference's order.
-fuse_kf_scw_mp_many and search_by_projection_ckf_scw_mp (k_scw_search) do it for LoopClosing's two Sim3 searches.
+fuse_kf_scw_mp_many and search_by_projection_ckf_scw_mp (k_scw_search) do it for LoopClosing's two Sim3 searches,
+and search_by_sim3 / search_by_sim3_many (k_sim3_search) for its mutual search: both directions of every candidate
+pair in one launch, nothing to replay in order.
 """
 from __future__ import annotations
 
@@ -608,9 +610,10 @@ def _tri_epipole(ex, ey, f2):
 
 
 def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off, scale,
-                   pt_f64, pt_desc, th, eps, u_right=None, inv_sigma2=None, blocked=None) -> dict:
-    """fuse_search_arrays (fuse, with u_right and inv_sigma2) and scw_search_arrays (not fuse, with blocked or
-    None): the conversion, the length checks, the outputs and the call."""
+                   pt_f64, pt_desc, th, eps, u_right=None, inv_sigma2=None, blocked=None, sim3=None) -> dict:
+    """fuse_search_arrays (fuse, with u_right and inv_sigma2), scw_search_arrays (not fuse, with blocked or None)
+    and sim3_search_arrays (not fuse, with sim3 = (srch_f64, srch_kf, srch_off, item_pt)): the conversion, the
+    length checks, the outputs and the call."""
     def arr(a, dt):
         return None if a is None else np.ascontiguousarray(a, dt)
     kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
@@ -637,12 +640,28 @@ def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_of
                 raise ValueError("a per-keyframe array is shorter than its offsets say")
         if blocked is not None and blocked.size < n:
             raise ValueError("blocked does not have one byte per feature")
+    grid = (ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale))
+    if sim3 is not None:
+        srch_f64 = np.ascontiguousarray(sim3[0], np.float64).reshape(-1, _lib.ORBFE_SIM3_F64)
+        srch_kf, srch_off, item_pt = arr(sim3[1], np.int32), arr(sim3[2], np.int64), arr(sim3[3], np.int32)
+        n_srch = len(srch_f64)
+        if srch_kf is None or srch_off is None or srch_kf.size != n_srch or srch_off.size != n_srch + 1:
+            raise ValueError("srch_kf / srch_off do not cover the searches")
+        n_items = int(srch_off[-1])
+        if n_items > 0 and (item_pt is None or item_pt.size < n_items):
+            raise ValueError("item_pt is shorter than srch_off says")
+        n_items = max(n_items, 0)
+        bi, bd, st = np.full(n_items, -1, np.int32), np.full(n_items, -1, np.int32), np.zeros(n_items, np.uint8)
+        out = _lib.Sim3Out(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
+        call("orbfe_sim3_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(desc), *grid, n_kf,
+             ptr(pt_f64), ptr(pt_desc), n_pts, ptr(srch_f64), ptr(srch_kf), ptr(srch_off), n_srch, ptr(item_pt),
+             float(th), float(eps), C.byref(out))
+        return dict(best_idx=bi, best_dist=bd, status=st)
     bi = np.full((n_kf, n_pts), -1, np.int32)
     bd = np.full((n_kf, n_pts), -1, np.int32)
     st = np.zeros((n_kf, n_pts), np.uint8)
     out = (_lib.FuseOut if fuse else _lib.ScwOut)(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data,
                                                   status=st.ctypes.data)
-    grid = (ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale))
     if fuse:
         entry, kf = "orbfe_fuse_search", (ptr(xy), ptr(octave), ptr(u_right), ptr(desc)) + grid + (ptr(inv_sigma2),)
     else:
@@ -675,6 +694,19 @@ def scw_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, c
     status (K, P) uint8 (ORBFE_FUSE_MARGINAL)."""
     return _search_arrays(False, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
                           scale, pt_f64, pt_desc, th, eps, blocked=blocked)
+
+
+def sim3_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off, scale,
+                       pt_f64, pt_desc, srch_f64, srch_kf, srch_off, item_pt, th, eps) -> dict:
+    """orbfe_sim3_search (k_sim3_search, include/orbfe.h): the search half of both directions of
+    ORBMatcher.search_by_sim3 (ORBMatcher.py:742-789 and :791-838) for many keyframe pairs in one launch.  The
+    keyframe arrays are scw_search_arrays' without blocked (each keyframe once; only the bounds, the inverse cell
+    sizes and the log scale factor of kf_f64 are read), pt_f64 (P, 9) / pt_desc (P, 32) one shared point table (the
+    normal is not read).  Search s has srch_f64[s] (28: fx fy cx cy, Rw, tw, sR, t), the target keyframe srch_kf[s]
+    and the items [srch_off[s], srch_off[s + 1]) of item_pt, rows of the point table.  Returns best_idx, best_dist
+    int32 (-1: no candidate) and status uint8 (ORBFE_FUSE_MARGINAL), flat over the items."""
+    return _search_arrays(False, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                          scale, pt_f64, pt_desc, th, eps, sim3=(srch_f64, srch_kf, srch_off, item_pt))
 
 
 # eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
@@ -1577,9 +1609,10 @@ class ORBMatcher:
         return slot, rows, descs, f32
 
     @staticmethod
-    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None):
-        """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse) or of
-        scw_search_arrays (with blocked)."""
+    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None):
+        """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse), of
+        scw_search_arrays (with blocked) or of sim3_search_arrays (with sim3 = (srch_f64, srch_kf, srch_off,
+        item_pt))."""
         def offs(lens):
             o = np.zeros(len(fr) + 1, np.int64)
             np.cumsum(lens, out=o[1:])
@@ -1592,6 +1625,8 @@ class ORBMatcher:
         pts = (np.array(rows, np.float64), np.stack(descs), th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
         if fuse:
             return fuse_search_arrays(*head, cat("u_right"), cat("desc"), *grid, cat("inv_sigma2"), *pts)
+        if sim3 is not None:
+            return sim3_search_arrays(*head, cat("desc"), *grid, *pts[:2], *sim3, *pts[2:])
         return scw_search_arrays(*head, cat("desc"), blocked, *grid, *pts)
 
     def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
@@ -2068,8 +2103,9 @@ class ORBMatcher:
                 best[i] = best_idx
         return best
 
-    # ORBMatcher.py:713-848
-    def search_by_sim3(self, pKF1, pKF2, vpMatches12, s12, R12, t12, th):
+    def _sim3_host(self, pKF1, pKF2, vpMatches12, s12, R12, t12, th):
+        """search_by_sim3 on the host, point by point (only the Hamming distances run on the device): the fallback
+        of the public method."""
         R1w, t1w = pKF1.get_rotation(), pKF1.get_translation()
         R2w, t2w = pKF2.get_rotation(), pKF2.get_translation()
         sR12 = s12 * R12
@@ -2095,6 +2131,201 @@ class ORBMatcher:
                 vpMatches12[i1] = vpMapPoints2[idx2]
                 n_found += 1
         return n_found, vpMatches12
+
+    def _sim3_one(self, pMP, Rw, tw, sR, t, pKFo, th, K):
+        """The best index in pKFo of one point, or -1, with the reference's own expressions on the objects
+        (ORBMatcher.py:746-789 / 795-838): _sim3_side for a single item; the few distances are host popcounts."""
+        fx, fy, cx, cy = K
+        with np.errstate(all="ignore"):
+            p3Dw = pMP.get_world_pos()
+            p3Dc = sR @ (Rw @ p3Dw + tw) + t
+            if p3Dc[2] < 0.0:
+                return -1
+            invz = 1.0 / p3Dc[2]
+            x, y = p3Dc[0] * invz, p3Dc[1] * invz
+            u, v = fx * x + cx, fy * y + cy
+            if not pKFo.is_in_image(u, v):
+                return -1
+            maxDistance = pMP.get_max_distance_invariance()
+            minDistance = pMP.get_min_distance_invariance()
+            dist3D = np.linalg.norm(p3Dc)
+            if not (minDistance <= dist3D <= maxDistance):
+                return -1
+            lvl = pMP.predict_scale(dist3D, pKFo)
+            vIndices = pKFo.get_features_in_area(u, v, th * pKFo.mvScaleFactors[lvl])
+        d = pMP.get_descriptor()
+        best_dist, best_idx = np.inf, -1
+        for idx in vIndices:
+            if not lvl - 1 <= pKFo.mvKeysUn[idx].octave <= lvl:
+                continue
+            dist = descriptor_distance(d, pKFo.mDescriptors[idx])
+            if dist < best_dist:
+                best_dist, best_idx = dist, idx
+        return best_idx if best_dist <= TH_HIGH else -1
+
+    @staticmethod
+    def _sim3_prep(N1, pKF2, vpMatches12, s12, R12, t12):
+        """What one pair adds to a k_sim3_search launch, or None when the arrays cannot express it (the pair then
+        takes _sim3_host): (_FuseFrame of pKF2, its map point list, (sR12, t12, sR21, t21) as the reference's
+        expressions give them, the same widened exactly as lists, whether any of them is float32)."""
+        if not (type(s12) in _TH_SET and np.isfinite(s12) and s12 != 0):
+            return None
+        if _pose_part(R12, (3, 3)) is None or _pose_part(t12, (3, 1)) is None:
+            return None
+        if not (isinstance(vpMatches12, list) and len(vpMatches12) == N1):
+            return None
+        f2 = _fuse_frame(pKF2)
+        if f2 is None:
+            return None
+        vp2 = pKF2.get_map_point_matches()
+        if len(vp2) != len(f2.xy):
+            return None
+        with np.errstate(all="ignore"):
+            sR12 = s12 * R12
+            sR21 = (1.0 / s12) * R12.T
+            t21 = -sR21 @ t12
+        sim3 = (sR12, t12, sR21, t21)
+        wide = [_pose_part(a, shape) for a, shape in zip(sim3, ((3, 3), (3, 1), (3, 3), (3, 1)))]
+        if any(w is None for w in wide):
+            return None
+        return f2, vp2, sim3, [w[0] for w in wide], any(w[1] for w in wide)
+
+    def _sim3_pairs(self, pKF1, pairs, th):
+        """search_by_sim3 of pKF1 with every (pKF2, vpMatches12, s12, R12, t12) of pairs from one k_sim3_search
+        launch of two searches per pair: per pair (n_found, vpMatches12), or None for a pair the arrays cannot
+        express (nothing of it was touched).  pKF1 is packed once and its live points are sent once; direction 1 of
+        a pair indexes them without that pair's already matched ones.  The two directions read nothing the call
+        writes, so the results are applied after the launch without an ordered replay."""
+        none = [None] * len(pairs)
+        if not (type(th) in _TH_SET and np.isfinite(th)):
+            return none
+        f1 = _fuse_frame(pKF1)
+        if f1 is None:
+            return none
+        vp1 = pKF1.get_map_point_matches()
+        N1 = len(vp1)
+        if N1 != len(f1.xy):
+            return none
+        preps = [self._sim3_prep(N1, *pr) for pr in pairs]
+        if all(p is None for p in preps):
+            return none
+        R1w, t1w = pKF1.get_rotation(), pKF1.get_translation()
+        K = (pKF1.fx, pKF1.fy, pKF1.cx, pKF1.cy)
+        skip = lambda p: not p or p.is_bad()  # noqa: E731
+        slot1, rows, descs, f32 = self._search_points(vp1, skip)
+        slot1 = np.array(slot1, np.int64)
+        f32 = f32 or f1.f32
+        frames, kf_at = [f1], {id(pKF1): 0}
+        srch_f64, srch_kf, srch_off, item_pt, work = [], [], [0], [], []
+        K1 = f1.f64[0:4].tolist()
+        for pr, pp in zip(pairs, preps):
+            if pp is None:
+                continue
+            pKF2, vpMatches12 = pr[0], pr[1]
+            f2, vp2, sim3, wide, s32 = pp
+            f32 = f32 or f2.f32 or s32
+            N2 = len(vp2)
+            already1, already2 = np.zeros(N1, bool), [False] * N2
+            for i, pMP in enumerate(vpMatches12):
+                if pMP:
+                    already1[i] = True
+                    idx2 = pMP.get_index_in_keyframe(pKF2)
+                    if 0 <= idx2 < N2:
+                        already2[idx2] = True
+            it1 = np.flatnonzero((slot1 >= 0) & ~already1)
+            alone1 = np.flatnonzero((slot1 == -1) & ~already1)
+            slot2, rows2, descs2, p32 = self._search_points([None if a else p for p, a in zip(vp2, already2)], skip)
+            slot2 = np.array(slot2, np.int64)
+            it2, alone2 = np.flatnonzero(slot2 >= 0), np.flatnonzero(slot2 == -1)
+            f32 = f32 or p32
+            if id(pKF2) not in kf_at:
+                kf_at[id(pKF2)] = len(frames)
+                frames.append(f2)
+            # direction 1 looks into pKF2 through (R1w, t1w) and (sR21, t21), direction 2 into pKF1 through
+            # (R2w, t2w) and (sR12, t12); both project with pKF1's intrinsics
+            srch_f64.append(K1 + f1.f64[5:17].tolist() + wide[2] + wide[3])
+            srch_f64.append(K1 + f2.f64[5:17].tolist() + wide[0] + wide[1])
+            srch_kf += [kf_at[id(pKF2)], 0]
+            item_pt += [slot1[it1], slot2[it2] + len(rows)]
+            srch_off += [srch_off[-1] + len(it1), srch_off[-1] + len(it1) + len(it2)]
+            rows += rows2
+            descs += descs2
+            work.append((pKF2, vpMatches12, vp2, sim3, it1, alone1, it2, alone2))
+        if srch_off[-1]:
+            res = self._search_launch(frames, rows, descs, th, f32, sim3=(
+                np.array(srch_f64, np.float64), np.array(srch_kf, np.int32), np.array(srch_off, np.int64),
+                np.concatenate(item_pt).astype(np.int32)))
+            bi, bd, st = res["best_idx"], res["best_dist"], res["status"]
+        out, results, s = [], iter(work), 0
+        for pp in preps:
+            if pp is None:
+                out.append(None)
+                continue
+            pKF2, vpMatches12, vp2, (sR12, t12, sR21, t21), it1, alone1, it2, alone2 = next(results)
+            R2w, t2w = pKF2.get_rotation(), pKF2.get_translation()
+            sides = []
+            for items, alone, vp, pose, pKFo in ((it1, alone1, vp1, (R1w, t1w, sR21, t21), pKF2),
+                                                 (it2, alone2, vp2, (R2w, t2w, sR12, t12), pKF1)):
+                best = np.full(len(vp), -1, np.int64)
+                redo = alone
+                if len(items):
+                    seg = slice(srch_off[s], srch_off[s + 1])
+                    b, d, m = bi[seg], bd[seg], st[seg] != 0
+                    ok = ~m & (d >= 0) & (d <= TH_HIGH)
+                    best[items[ok]] = b[ok]
+                    redo = np.concatenate([alone, items[m]])
+                for i in redo.tolist():
+                    best[i] = self._sim3_one(vp[i], *pose, pKFo, th, K)
+                sides.append(best.tolist())
+                s += 1
+            vnMatch1, vnMatch2 = sides
+            n_found = 0
+            for i1, idx2 in enumerate(vnMatch1):
+                if idx2 >= 0 and vnMatch2[idx2] == i1:
+                    vpMatches12[i1] = vp2[idx2]
+                    n_found += 1
+            out.append((n_found, vpMatches12))
+        return out
+
+    # ORBMatcher.py:713-848
+    def search_by_sim3(self, pKF1, pKF2, vpMatches12, s12, R12, t12, th):
+        """LoopClosing.compute_sim3's mutual search (LoopClosing.py:203) from one k_sim3_search launch of two
+        searches: pKF1's map points into pKF2 through (R1w, t1w) and (sR21, t21), and pKF2's into pKF1 through
+        (R2w, t2w) and (sR12, t12), with sR12, sR21 and t21 from the reference's expressions on the host.  The
+        prefilter (not pMP or already matched or pMP.is_bad()) and the already-matched flags are taken once on the
+        host and only surviving points are sent.  An item that came back ORBFE_FUSE_MARGINAL, or whose point the
+        arrays cannot express, is redone alone with the reference's expressions (_sim3_one); otherwise the device's
+        candidate counts when best_dist <= TH_HIGH.  The mutual check and the writes into vpMatches12 follow on the
+        host in list order.  Neither direction reads what the call writes, so nothing is replayed in order.  The
+        host body (_sim3_host) runs instead when _fuse_frame refuses either keyframe (or a keyframe does not have
+        one map point slot per feature), when R12 / t12 is not a finite (3, 3) / (3, 1) float32 / float64 array,
+        when s12 is not a plain finite non-zero number or the Sim3 parts it gives are not finite, when th is not a
+        plain finite number, or when vpMatches12 is not a list with one entry per map point slot of pKF1.  It also
+        runs where the HIP runtime sees no device, as for search_by_projection_ckf_scw_mp."""
+        if _lib.device_present():
+            r = self._sim3_pairs(pKF1, [(pKF2, vpMatches12, s12, R12, t12)], th)[0]
+            if r is not None:
+                return r
+        return self._sim3_host(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+
+    def search_by_sim3_many(self, pKF1, kfs2, vpMatches12s, s12s, R12s, t12s, th):
+        """What this list holds, list for list, from one k_sim3_search launch of two searches per candidate:
+
+            [self.search_by_sim3(pKF1, kf, v, s, R, t, th)
+             for kf, v, s, R, t in zip(kfs2, vpMatches12s, s12s, R12s, t12s)]
+
+        pKF1 is packed once and its live map points are sent once for all candidates.  A candidate whose keyframe
+        or Sim3 the arrays cannot express (see search_by_sim3) takes the single call at its place.  The loop itself
+        runs when two candidates share one vpMatches12 list object (the second would read what the first wrote) and
+        where the HIP runtime sees no device."""
+        cols = [list(c) for c in (kfs2, vpMatches12s, s12s, R12s, t12s)]
+        pairs = list(zip(*cols))
+        if any(len(c) != len(pairs) for c in cols):
+            raise ValueError("one vpMatches12, s12, R12 and t12 per keyframe")
+        res = [None] * len(pairs)
+        if _lib.device_present() and len({id(pr[1]) for pr in pairs}) == len(pairs):
+            res = self._sim3_pairs(pKF1, pairs, th)
+        return [self.search_by_sim3(pKF1, *pr, th) if r is None else r for pr, r in zip(pairs, res)]
 
     @staticmethod
     def _ckf_pose(Scw):

@@ -1,11 +1,12 @@
-// fuse_validate.hip — host-side sanitizer check of the argument validation of orbfe_fuse_search and
-// orbfe_scw_search.
+// fuse_validate.hip — host-side sanitizer check of the argument validation of orbfe_fuse_search,
+// orbfe_scw_search and orbfe_sim3_search.
 //
 // A program of its own: it links orbfe_fuse.hip alone and calls the entries only with arguments that the validation
 // refuses (or with nothing to do), all of which return before any device call, so it runs on a machine without a
 // GPU.  What orbfe_scw_search accepts where orbfe_fuse_search refuses (a null blocked, anything in slot 4 of the
 // keyframe scalars) would reach the device on its own, so each is paired with one later refusal and the message must
-// be that later one's.  Build and run with tools/dbg/fuse_validate_asan.sh (host code under
+// be that later one's; likewise for what orbfe_sim3_search accepts (anything in slots 0-19 of a keyframe's scalars
+// and in the normal of a point).  Build and run with tools/dbg/fuse_validate_asan.sh (host code under
 // -fsanitize=address,undefined).
 #include <cmath>
 #include <cstdint>
@@ -158,6 +159,108 @@ void refusals() {
     }
 }
 
+// orbfe_sim3_search: Input's keyframe and points, three searches (two items, none, one item)
+struct Sim3Input : Input {
+    std::vector<double> sf = std::vector<double>(3 * ORBFE_SIM3_F64, 0.5);
+    std::vector<int32_t> skf = {0, 0, 0}, item = {1, 0, 1};
+    std::vector<int64_t> soff = {0, 2, 2, 3};
+    std::vector<int32_t> bi3 = {-7, -7, -7}, bd3 = {-7, -7, -7};
+    std::vector<uint8_t> st3 = {7, 7, 7};
+    int32_t n_srch = 3;
+
+    int run3() {
+        orbfe_sim3_out o{p(bi3), p(bd3), p(st3)};
+        return orbfe_sim3_search(p(kf), p(ki), p(off), p(xy), p(octave), p(desc), p(cell_at), p(cell_off), p(idx_at),
+                                 p(cell_idx), p(lvl_off), p(scale), n_kf, p(pt), p(pdesc), n_pts, p(sf), p(skf),
+                                 p(soff), n_srch, p(item), th, eps, null_out ? nullptr : &o);
+    }
+    bool untouched3() const {
+        for (int i = 0; i < 3; ++i)
+            if (bi3[i] != -7 || bd3[i] != -7 || st3[i] != 7) return false;
+        return true;
+    }
+};
+
+void expect3(const char* what, int want, const std::function<void(Sim3Input&)>& breakit, const char* message = "") {
+    Sim3Input in;
+    breakit(in);
+    orbfe::g_err.clear();
+    const int rc = in.run3();
+    ++checks;
+    if (rc != want || !in.untouched3() || orbfe::g_err.find(message) == std::string::npos) {
+        std::printf("FAIL sim3 %s: rc %d (want %d), outputs %s, message: %s (want: %s)\n", what, rc, want,
+                    in.untouched3() ? "untouched" : "WRITTEN", orbfe::g_err.c_str(), message);
+        ++failures;
+    }
+}
+
+void sim3_refusals() {
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    const int E = ORBFE_EINVAL;
+    expect3("negative keyframe count", E, [](Sim3Input& i) { i.n_kf = -1; });
+    expect3("negative point count", E, [](Sim3Input& i) { i.n_pts = -1; });
+    expect3("negative search count", E, [](Sim3Input& i) { i.n_srch = -1; });
+    expect3("too many keyframes", E, [](Sim3Input& i) { i.n_kf = 65536; });
+    expect3("th nan", E, [&](Sim3Input& i) { i.th = nan; });
+    expect3("eps negative", E, [](Sim3Input& i) { i.eps = -1.0; });
+    expect3("no searches", ORBFE_OK, [](Sim3Input& i) { i.n_srch = 0; });
+    expect3("no items", ORBFE_OK, [](Sim3Input& i) { i.soff = {0, 0, 0, 0}; });
+    expect3("null out", E, [](Sim3Input& i) { i.null_out = true; });
+#define NULL3(field) expect3("null " #field, E, [](Sim3Input& i) { i.skip = i.field.data(); }, "null argument")
+    NULL3(kf);
+    NULL3(ki);
+    NULL3(off);
+    NULL3(xy);
+    NULL3(octave);
+    NULL3(desc);
+    NULL3(cell_at);
+    NULL3(cell_off);
+    NULL3(idx_at);
+    NULL3(cell_idx);
+    NULL3(lvl_off);
+    NULL3(scale);
+    NULL3(pt);
+    NULL3(pdesc);
+    NULL3(sf);
+    NULL3(skf);
+    NULL3(soff);
+    NULL3(item);
+    NULL3(bi3);
+    NULL3(bd3);
+    NULL3(st3);
+    expect3("srch_off[0] not 0", E, [](Sim3Input& i) { i.soff[0] = 1; }, "srch_off[0]");
+    expect3("srch_off decreases", E, [](Sim3Input& i) { i.soff[2] = 1; }, "search 1");
+    expect3("target past the keyframes", E, [](Sim3Input& i) { i.skf[2] = 1; }, "search 2");
+    expect3("target negative", E, [](Sim3Input& i) { i.skf[0] = -1; }, "search 0");
+    expect3("item past the points", E, [](Sim3Input& i) { i.item[2] = 2; }, "outside the point table");
+    expect3("item negative", E, [](Sim3Input& i) { i.item[0] = -1; }, "outside the point table");
+    for (int c = 0; c < 3 * ORBFE_SIM3_F64; ++c)
+        expect3("search scalar nan", E, [&](Sim3Input& i) { i.sf[c] = c % 2 ? nan : -inf; }, "a scalar is not finite");
+    expect3("off[0] not 0", E, [](Sim3Input& i) { i.off[0] = 1; });
+    expect3("level count 0", E, [](Sim3Input& i) { i.ki[2] = 0; });
+    expect3("grid entry past the features", E, [](Sim3Input& i) { i.cell_idx[1] = 2; });
+    expect3("octave negative", E, [](Sim3Input& i) { i.octave[0] = -1; });
+    expect3("coordinate inf", E, [&](Sim3Input& i) { i.xy[3] = inf; });
+    expect3("scale nan", E, [&](Sim3Input& i) { i.scale[1] = nan; });
+    for (int c = 20; c < ORBFE_FUSE_KF_F64; ++c)
+        expect3("keyframe scalar nan", E, [&](Sim3Input& i) { i.kf[c] = nan; }, "a scalar is not finite");
+    const char* later = "a point scalar is not finite";
+    for (int c = 0; c < 2 * ORBFE_FUSE_PT_F64; ++c) {
+        if (c % ORBFE_FUSE_PT_F64 >= 3 && c % ORBFE_FUSE_PT_F64 < 6) continue;  // the normal: not read, see below
+        expect3("point scalar nan", E, [&](Sim3Input& i) { i.pt[c] = nan; }, later);
+    }
+    // accepted by the validation: the refusal is the later one, of the point scalar
+    for (int c = 0; c < 20; ++c)
+        expect3("unread keyframe slot goes on", E, [&](Sim3Input& i) { i.kf[c] = nan, i.pt[8] = inf; }, later);
+    for (int c = 3; c < 6; ++c)
+        expect3("normal goes on", E, [&](Sim3Input& i) { i.pt[c] = -inf, i.pt[ORBFE_FUSE_PT_F64] = nan; }, later);
+    float ms = -1.f;
+    if (orbfe_sim3_search_last_ms(nullptr) != E || orbfe_sim3_search_last_ms(&ms) != ORBFE_OK || ms != 0.f) {
+        std::printf("FAIL sim3 last_ms\n");
+        ++failures;
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -165,6 +268,7 @@ int main() {
         scw = s;
         refusals();
     }
+    sim3_refusals();
     std::printf("%d checks, %d failures\n", checks, failures);
     return failures ? 1 : 0;
 }
