@@ -43,7 +43,8 @@ extern "C" {
                                * orbfe_kfdb_query_many, orbfe_kfdb_query_many_device, orbfe_kfdb_set_scratch_limit,
                                * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out, and orbfe_scw_search,
                                * orbfe_scw_search_last_ms and orbfe_scw_out, and orbfe_sim3_search,
-                               * orbfe_sim3_search_last_ms and orbfe_sim3_out */
+                               * orbfe_sim3_search_last_ms and orbfe_sim3_out, and orbfe_fkf_search,
+                               * orbfe_fkf_search_last_ms and orbfe_fkf_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -785,6 +786,60 @@ int orbfe_sim3_search(const double* kf_f64, const int32_t* kf_i32, const int64_t
                       const int32_t* item_pt, double th, double eps, const orbfe_sim3_out* out);
 /* Kernel time of the last orbfe_sim3_search (ms, HIP events), for measurement. */
 int orbfe_sim3_search_last_ms(float* ms);
+
+/* ---- relocalisation's projection search into a frame (ORBMatcher.search_by_projection_f_kf_f,
+ *      ORBMatcher.py:924-1008, with Frame.get_features_in_area, Frame.py:373-416) ----
+ *
+ * k_fkf_search, one launch for n_srch searches.  A search is a target frame and a list of map points of its own
+ * (a keyframe's, after the caller's prefilter).  The ORBdist test, the assignment into the frame's map point slots
+ * (:985-987) and the rotation histogram stay with the caller, in the reference's order; because an assignment takes
+ * a feature away from the items after it, the caller redoes an item whose best feature was taken meanwhile.
+ * The target arrays are orbfe_scw_search's, `blocked` included (a frame that several searches target appears once,
+ * and its blocked bytes serve all of them); the point table is orbfe_fuse_search's.  The searches are
+ * orbfe_sim3_search's without the search scalars: srch_kf[s] is the target, items [srch_off[s], srch_off[s + 1])
+ * of item_pt index the point table (repeats allowed, any order).
+ * What differs from orbfe_scw_search:
+ *   - the launch is ragged and the outputs are flat over the items, as in orbfe_sim3_search; there is no out_stride;
+ *   - the target is a Frame: grid columns and rows are FRAME_GRID_COLS / FRAME_GRID_ROWS, the level count and tables
+ *     the frame's; the pose slots [5..16] are mTcw's rotation and translation and [17..19] Ow = -Rcw^T tcw as the
+ *     caller computed it with the reference's expression, widened exactly;
+ *   - there is no depth gate: pc.z < 0 goes on, so a point behind the camera whose u, v land inside the bounds is
+ *     searched.  status gets ORBFE_FUSE_MARGINAL (and the item no candidate) when pc.z is 0 or within its bound of
+ *     0, or when u, v or a bound of theirs is not finite;
+ *   - u = (fx * pc.x) * invz + cx and v = (fy * pc.y) * invz + cy, in this order (the reference's fx * xc * invzc);
+ *   - the image gate is inclusive at both ends: mnMinX <= u <= mnMaxX and mnMinY <= v <= mnMaxY;
+ *   - there is no viewing gate; slots [3..5] of a point (the normal) are not read and may hold anything, non-finite
+ *     values included;
+ *   - both ends of the cell window truncate toward zero: trunc(((u - mnMinX) - r) * widthInv), at least 0, empty when
+ *     >= columns; trunc(((u - mnMinX) + r) * widthInv), at most columns - 1, empty when negative (rows likewise).
+ *     A bound in (-1, 1) is cell 0, so only a bound near an integer of magnitude >= 1 marks;
+ *   - a candidate's octave lies in [level - 1, level + 1], three octaves instead of two.
+ * The rest is orbfe_scw_search's: PO = p - Ow, dist = sqrt(PO.PO) in [min, max] distance, level =
+ * ceil(log(mfMaxDistance / dist) / mfLogScaleFactor) clamped to [0, levels - 1], r = th * scale[level], the visiting
+ * order, |x - u| < r and |y - v| < r, a blocked entry skipped first and marking nothing, the smallest Hamming distance
+ * and among equals the earliest visited, and the margins scaled by eps.
+ * Outputs at [i], i < srch_off[n_srch]: best_idx (feature index of the target or -1), best_dist (Hamming distance
+ * or -1), status.  The limits are orbfe_fuse_search's.  A workgroup takes up to ORBFE_FUSE_CHUNK items of one search;
+ * an empty search launches nothing. */
+typedef struct orbfe_fkf_out {
+    int32_t* best_idx;  /* one per item */
+    int32_t* best_dist; /* one per item */
+    uint8_t* status;    /* one per item */
+} orbfe_fkf_out;
+/* Host buffers, synchronous; the target arrays and their checks are orbfe_scw_search's (slot [4] of a block is exempt
+ * from the finiteness check), the searches' checks orbfe_sim3_search's: ORBFE_EINVAL, before any device call, for a
+ * srch_kf outside [0, n_kf), srch_off[0] != 0 or a srch_off that decreases, an item_pt outside [0, n_pts), a point
+ * scalar outside slots [3..5] that is not finite.  n_srch == 0 or srch_off[n_srch] == 0 launches nothing and succeeds.
+ * Process-wide buffers, stream and events of its own: concurrent callers take turns, and none of them waits for a
+ * caller of the other three searches. */
+int orbfe_fkf_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                     const int32_t* octave, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+                     const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                     const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                     const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt,
+                     double th, double eps, const orbfe_fkf_out* out);
+/* Kernel time of the last orbfe_fkf_search (ms, HIP events), for measurement. */
+int orbfe_fkf_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

@@ -89,6 +89,11 @@ class Sim3Out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
 
 
+class FkfOut(C.Structure):
+    """orbfe_fkf_out: caller-owned output arrays of orbfe_fkf_search, flat over the items."""
+    _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
+
+
 class KfdbManyOut(C.Structure):
     """orbfe_kfdb_many_out: caller-owned host arrays of orbfe_kfdb_query_many / _many_device."""
     _fields_ = [(k, C.c_void_p) for k in ("n_sharing", "max_common", "n_hits", "hit_slot", "hit_common", "hit_first",
@@ -218,6 +223,9 @@ SIGNATURES = {
                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double,
                                               C.POINTER(Sim3Out)],
     "orbfe_sim3_search_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_fkf_search": [C.c_void_p] * 13 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_double, C.c_double, C.POINTER(FkfOut)],
+    "orbfe_fkf_search_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -2,7 +2,8 @@
 // call in one launch on gfx950: ORBMatcher.fuse_pkf_mp (ORBMatcher.py:498-567) as k_fuse_search, and LoopClosing's two
 // Sim3 searches, ORBMatcher.fuse_kf_scw_mp (:395-480) and ORBMatcher.search_by_projection_ckf_scw_mp (:850-922), as
 // k_scw_search; and the two directions of ORBMatcher.search_by_sim3 (:713-848) for many keyframe pairs as
-// k_sim3_search.  All three kernels are instantiations of one body, proj_search<kMode>.
+// k_sim3_search; and relocalisation's ORBMatcher.search_by_projection_f_kf_f (:924-1008) into many frames as
+// k_fkf_search.  All four kernels are instantiations of one body, proj_search<kMode>.
 //
 // The reference projects each map point into a keyframe, gates it (depth sign, image bounds, scale-invariance
 // distances, viewing angle), predicts its pyramid level, searches the keyframe's grid in a window of radius
@@ -12,7 +13,7 @@
 // dist < bestDist.  None of this reads what a fusion changes, so it runs here for all items at once and the caller
 // applies the matches afterwards in the reference's order.
 //
-// What the three variants do not share:
+// What the four variants do not share:
 //   k_fuse_search  also projects the right coordinate ur = u - bf / z and filters the candidates by a chi-square on
 //                  the reprojection error (three terms against 7.8 for a stereo feature, two against 5.99 for a mono
 //                  one).
@@ -30,6 +31,17 @@
 //                  so the Sim3's scale moves the level.  Its launch is ragged: a search is a target, a pose and a
 //                  list of rows of the shared point table, and a 1-D grid runs over a host-built table of (search,
 //                  first item) chunks, so no workgroup straddles two searches and an empty search launches nothing.
+//
+//   k_fkf_search   searches a Frame, not a KeyFrame (Frame.get_features_in_area, Frame.py:373-416), with
+//                  k_sim3_search's ragged launch (a search is a target frame and a list of rows of the point table;
+//                  there are no search scalars, the pose and the intrinsics are the target block's) and
+//                  k_scw_search's blocked byte.  It has no depth gate: a point behind the camera whose u, v land
+//                  inside the bounds is searched, and only |z| within its bound of 0 (or 1 / z, u or v not finite)
+//                  marks.  u is (fx * xc) * invz + cx, the reference's order.  The image bounds are inclusive at both
+//                  ends.  The distance is |p - Ow| as in k_scw_search; there is no viewing gate and the normal is not
+//                  read.  Both ends of the cell window truncate toward zero (int()), so a bound in (-1, 1) is cell 0
+//                  and only the integers of magnitude >= 1 can flip one.  A candidate's octave lies in
+//                  [level - 1, level + 1]: three octaves, the others keep two.
 //
 // The depth gate: fuse_pkf_mp and fuse_kf_scw_mp skip z < 0, the ckf search z <= 0.  At z == 0 the first two run on to
 // 1 / 0, u and v become inf or NaN and fail the image test, so all three skip the point and one code path serves them.
@@ -80,7 +92,7 @@ struct PsKfs {
     const double *u_right, *inv_sigma2;  // k_fuse_search only
     const int32_t *octave, *cell_off, *cell_idx;
     const uint8_t* desc;
-    const uint8_t* blocked;  // k_scw_search only, and there null when nothing is blocked
+    const uint8_t* blocked;  // k_scw_search and k_fkf_search only, and there null when nothing is blocked
 };
 
 struct PsPts {
@@ -92,19 +104,19 @@ struct PsPts {
 struct PsOut {
     int32_t *best_idx, *best_dist;
     uint8_t* status;
-    int64_t stride;  // k_sim3_search: not read, the outputs are flat over the items
+    int64_t stride;  // k_sim3_search, k_fkf_search: not read, the outputs are flat over the items
 };
 
-// k_sim3_search only: the searches, their items and the launch's chunk table
+// k_sim3_search and k_fkf_search: the searches, their items and the launch's chunk table
 struct PsSim3 {
-    const double* f64;       // kPsSim3F64 per search
+    const double* f64;       // kPsSim3F64 per search; k_fkf_search: null, a search has no scalars of its own
     const int32_t* kf;       // target keyframe per search
     const int64_t* off;      // search s owns items [off[s], off[s + 1])
     const int32_t* item_pt;  // point table row per item
     const int64_t* chunk;    // (search, first item) per workgroup
 };
 
-enum PsMode { kPsFuse, kPsScw, kPsSim3 };
+enum PsMode { kPsFuse, kPsScw, kPsSim3, kPsFkf };
 
 // every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
 // is this one exactly
@@ -114,17 +126,20 @@ template <PsMode kMode>
 __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, double th, double eps,
                                             const PsOut& out, [[maybe_unused]] const PsSim3& sx) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode == kPsScw, kSim3 = kMode == kPsSim3;
+    constexpr bool kFkf = kMode == kPsFkf;
+    constexpr bool kRagged = kSim3 || kFkf;  // a 1-D grid over the chunk table, outputs flat over the items
+    constexpr bool kBlocked = kScw || kFkf;
     __shared__ double s_u[kPsChunk], s_v[kPsChunk], s_eu[kPsChunk], s_ev[kPsChunk], s_r[kPsChunk];
     __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, in k_fuse_search only
     __shared__ int16_t s_x0[kPsChunk], s_x1[kPsChunk], s_y0[kPsChunk], s_y1[kPsChunk], s_lvl[kPsChunk];
     __shared__ uint8_t s_st[kPsChunk];
     const int tid = threadIdx.x;
     // the workgroup's keyframe, its first item and the end of its item range: (keyframe, chunk of the shared
-    // points) of a 2-D grid, or in k_sim3_search the chunk table's (search, first item) and the search's target
+    // points) of a 2-D grid, or in the ragged kernels the chunk table's (search, first item) and the search's target
     [[maybe_unused]] int srch = 0;
     int k;
     int64_t first, n_end;
-    if constexpr (kSim3) {
+    if constexpr (kRagged) {
         srch = (int)sx.chunk[2 * (int64_t)blockIdx.x];
         first = sx.chunk[2 * (int64_t)blockIdx.x + 1];
         n_end = sx.off[srch + 1];
@@ -146,7 +161,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
         const int64_t i = first + tid;
         if (i < n_end) {
             const double* P;
-            if constexpr (kSim3)
+            if constexpr (kRagged)
                 P = pt.f64 + (int64_t)sx.item_pt[i] * kPsPtF64;
             else
                 P = pt.f64 + i * kPsPtF64;
@@ -195,15 +210,24 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                         break;
                     }
                 }
-                if (zc < 0.0) {
+                if constexpr (kFkf) {
+                    // no depth gate: the sign of zc decides nothing, but within its bound of 0 nothing after it is
+                    // known, and at zc == 0 the reference divides by zero; the caller's redo follows it there
+                    if (zc == 0.0 || fabs(zc) < Ez) {
+                        st = ORBFE_FUSE_MARGINAL;
+                        break;
+                    }
+                } else if (zc < 0.0) {
                     if (-zc < Ez) st = ORBFE_FUSE_MARGINAL;
                     break;
                 }
                 // zc == 0 runs on: 1 / 0 is inf, u and v end as inf or NaN and fail the image test below (the ckf
                 // search leaves at its z <= 0; neither way reaches a window)
                 const double iz = 1.0 / zc;
-                const double xn = xc * iz, yn = yc * iz;
-                const double fxx = fx * xn, fyy = fy * yn;
+                // k_fkf_search multiplies in the reference's order there, (fx * xc) * iz: xn, yn are then fx * xc and
+                // fy * yc, and fxx, fyy again the products the principal point is added to
+                const double xn = kFkf ? fx * xc : xc * iz, yn = kFkf ? fy * yc : yc * iz;
+                const double fxx = kFkf ? xn * iz : fx * xn, fyy = kFkf ? yn * iz : fy * yn;
                 u = fxx + cx;
                 v = fyy + cy;
                 [[maybe_unused]] double bz = 0.0;
@@ -211,17 +235,29 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     bz = bf * iz;
                     ur = u - bz;
                 }
-                const bool in = minX <= u && u < maxX && minY <= v && v < maxY;
-                if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
-                if (zc == 0.0) break;  // not in the image (in is false), whatever xc and yc are
-                const double rz = Ez / zc;
+                // Frame's bounds are inclusive at both ends
+                const bool in = kFkf ? !(u < minX || u > maxX || v < minY || v > maxY)
+                                     : minX <= u && u < maxX && minY <= v && v < maxY;
+                if constexpr (!kFkf) {
+                    if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
+                    if (zc == 0.0) break;  // not in the image (in is false), whatever xc and yc are
+                }
+                const double rz = Ez / (kFkf ? fabs(zc) : zc);
                 if (!(rz <= 0.25)) st = ORBFE_FUSE_MARGINAL;
-                const double Eiz = iz * (2.0 * rz + 2.0 * eps);
-                const double Ax = fabs(xc) * Eiz + Ex * (iz + Eiz), Ay = fabs(yc) * Eiz + Ey * (iz + Eiz);
+                const double aiz = kFkf ? fabs(iz) : iz;
+                const double Eiz = aiz * (2.0 * rz + 2.0 * eps);
+                const double Ax = kFkf ? fabs(fx) * Ex : fabs(xc) * Eiz + Ex * (iz + Eiz),
+                             Ay = kFkf ? fabs(fy) * Ey : fabs(yc) * Eiz + Ey * (iz + Eiz);
                 const double Exn = Ax + eps * (fabs(xn) + Ax), Eyn = Ay + eps * (fabs(yn) + Ay);
                 const double Mu = fabs(fxx) + fabs(cx), Mv = fabs(fyy) + fabs(cy);
-                Eu = fabs(fx) * Exn + 4.0 * eps * Mu;
-                Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
+                if constexpr (kFkf) {
+                    const double Bx = fabs(xn) * Eiz + Exn * (aiz + Eiz), By = fabs(yn) * Eiz + Eyn * (aiz + Eiz);
+                    Eu = (Bx + eps * (fabs(fxx) + Bx)) + 4.0 * eps * Mu;
+                    Ev = (By + eps * (fabs(fyy) + By)) + 4.0 * eps * Mv;
+                } else {
+                    Eu = fabs(fx) * Exn + 4.0 * eps * Mu;
+                    Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
+                }
                 double sum;  // finite when everything phase 2 reads is
                 if constexpr (!kFuse) {
                     sum = ((u + v) + Eu) + Ev;
@@ -260,7 +296,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 if (fabs(dist - minD) < Ed + eps * fabs(minD) || fabs(dist - maxD) < Ed + eps * fabs(maxD))
                     st = ORBFE_FUSE_MARGINAL;
                 if (dist < minD || dist > maxD) break;
-                if constexpr (!kSim3) {  // search_by_sim3 has no viewing gate, and does not read the normal
+                if constexpr (!kSim3 && !kFkf) {  // neither has a viewing gate, and neither reads the normal
                     const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
                     const double dot = (t0 + t1) + t2;
                     const double half = 0.5 * dist;
@@ -292,6 +328,23 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 }
                 const double Ewx = fabs(winv) * (Eu + 4.0 * eps * ((fabs(u) + fabs(minX)) + fabs(r)));
                 const double Ewy = fabs(hinv) * (Ev + 4.0 * eps * ((fabs(v) + fabs(minY)) + fabs(r)));
+                if constexpr (kFkf) {
+                    // int() truncates toward zero at both ends: (-1, 1) is cell 0, so only an integer of magnitude
+                    // >= 1 separates two outcomes (max(0, .) hides the negative ones of a lower end, harmlessly
+                    // marked here)
+                    if ((fabs(ax) > 0.5 && near_int(ax, Ewx)) || (fabs(bx) > 0.5 && near_int(bx, Ewx)) ||
+                        (fabs(ay) > 0.5 && near_int(ay, Ewy)) || (fabs(by) > 0.5 && near_int(by, Ewy)))
+                        st = ORBFE_FUSE_MARGINAL;
+                    const double tax = trunc(ax), tbx = trunc(bx), tay = trunc(ay), tby = trunc(by);
+                    // the four early returns of Frame.get_features_in_area
+                    if (tax >= (double)cols || tbx < 0.0 || tay >= (double)rows || tby < 0.0) break;
+                    x0 = tax < 0.0 ? 0 : (int)tax;
+                    x1 = tbx > (double)(cols - 1) ? cols - 1 : (int)tbx;
+                    y0 = tay < 0.0 ? 0 : (int)tay;
+                    y1 = tby > (double)(rows - 1) ? rows - 1 : (int)tby;
+                    lvl = level;
+                    break;
+                }
                 if (near_int(ax, Ewx) || near_int(bx, Ewx) || near_int(ay, Ewy) || near_int(by, Ewy))
                     st = ORBFE_FUSE_MARGINAL;
                 const double fax = floor(ax), cbx = ceil(bx), fay = floor(ay), cby = ceil(by);
@@ -331,7 +384,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
     const int32_t* cidx = kf.cell_idx + kf.idx_at[k];
     [[maybe_unused]] const double *uright = nullptr, *is2 = nullptr;
     [[maybe_unused]] const uint8_t* blk = nullptr;
-    if constexpr (kScw) {
+    if constexpr (kBlocked) {
         blk = kf.blocked ? kf.blocked + base : nullptr;
     } else if constexpr (kFuse) {
         uright = kf.u_right + base;
@@ -352,7 +405,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
             }
             const int x0 = s_x0[j], x1 = s_x1[j], y0 = s_y0[j], y1 = s_y1[j];
             const uint4* pd;
-            if constexpr (kSim3)
+            if constexpr (kRagged)
                 pd = reinterpret_cast<const uint4*>(pt.desc + (int64_t)sx.item_pt[i] * 32);
             else
                 pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
@@ -362,7 +415,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 const int a = coff[ix * rows + y0], b = coff[ix * rows + y1 + 1];
                 for (int pos = a + l; pos < b; pos += kPsGroup) {
                     const int f = cidx[pos];
-                    if constexpr (kScw)
+                    if constexpr (kBlocked)
                         if (blk && blk[f]) continue;
                     const double kx = xy[2 * f], ky = xy[2 * f + 1];
                     const double dx = kx - u, dy = ky - v;
@@ -370,7 +423,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     if (fabs(fabs(dx) - r) < Edx + er_r || fabs(fabs(dy) - r) < Edy + er_r) st = ORBFE_FUSE_MARGINAL;
                     if (!(fabs(dx) < r && fabs(dy) < r)) continue;
                     const int o = oct[f];
-                    if (o < level - 1 || o > level) continue;
+                    if (o < level - 1 || o > level + (kFkf ? 1 : 0)) continue;
                     if constexpr (kFuse) {
                         const double kr = uright[f];
                         const double ex = u - kx, ey = v - ky;
@@ -406,7 +459,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
             }
         }
         if (l == 0) {
-            const int64_t at = kSim3 ? i : (int64_t)k * out.stride + i;
+            const int64_t at = kRagged ? i : (int64_t)k * out.stride + i;
             out.best_idx[at] = key == kPsNone ? -1 : cidx[key & 0xFFFFu];
             out.best_dist[at] = key == kPsNone ? -1 : (int)(key >> 16);
             out.status[at] = (uint8_t)st;
@@ -428,13 +481,19 @@ __global__ __launch_bounds__(kPsChunk) void k_sim3_search(PsKfs kf, PsPts pt, do
     proj_search<kPsSim3>(kf, pt, th, eps, out, sx);
 }
 
+// the same grid; sx.f64 is null: the pose and the intrinsics are the target frame's block
+__global__ __launch_bounds__(kPsChunk) void k_fkf_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out,
+                                                         PsSim3 sx) {
+    proj_search<kPsFkf>(kf, pt, th, eps, out, sx);
+}
+
 }  // namespace orbfe
 
 namespace {
 
 // scratch of one entry: process-wide, created on first use and never torn down (the HIP runtime may already be gone
 // when static destructors run); callers of that entry on several threads take turns.  Each entry has an instance of
-// its own, so the three do not wait for each other and each last_ms is its own entry's.
+// its own, so the four do not wait for each other and each last_ms is its own entry's.
 struct Searcher {
     std::mutex mu;
     DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, blocked bytes, status
@@ -443,7 +502,7 @@ struct Searcher {
     DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, srch_kf, item_pt, best_idx, best_dist
     std::vector<int32_t> h_i32;
     std::vector<uint8_t> h_st;
-    std::vector<int64_t> h_chunk;  // k_sim3_search: (search, first item) per workgroup
+    std::vector<int64_t> h_chunk;  // k_sim3_search, k_fkf_search: (search, first item) per workgroup
     hipStream_t stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.f;
@@ -464,20 +523,20 @@ bool all_finite(const double* v, int64_t n) {
 
 size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// what orbfe_sim3_search has besides the keyframes and the point table
+// what orbfe_sim3_search and orbfe_fkf_search have besides the keyframes and the point table
 struct Sim3In {
-    const double* f64;
+    const double* f64;  // orbfe_fkf_search: null
     const int32_t* kf;
     const int64_t* off;
     int32_t n;
     const int32_t* item_pt;
 };
 
-// All three entries: validate, stage, launch, download.  Not kPsFuse: u_right and inv_sigma2 are not looked at and
-// slot 4 of a keyframe's scalars may hold anything.  kPsScw: blocked may be null (nothing is blocked); otherwise
-// blocked is not looked at.  kPsSim3: sx is the searches, slots 0-19 of a keyframe's scalars and 3-5 of a point's may
-// hold anything, out_stride is not looked at and the outputs are flat over the items.  Out is the entry's
-// orbfe_*_out.
+// All four entries: validate, stage, launch, download.  Not kPsFuse: u_right and inv_sigma2 are not looked at and
+// slot 4 of a keyframe's scalars may hold anything.  kPsScw, kPsFkf: blocked may be null (nothing is blocked);
+// otherwise blocked is not looked at.  kPsSim3, kPsFkf: sx is the searches, slots 3-5 of a point's scalars may hold
+// anything, out_stride is not looked at and the outputs are flat over the items; kPsSim3 alone has search scalars and
+// lets slots 0-19 of a keyframe's scalars hold anything.  Out is the entry's orbfe_*_out.
 template <PsMode kMode, class Out>
 void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy, const int32_t* octave,
             const double* u_right, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
@@ -486,12 +545,13 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride,
             [[maybe_unused]] const Sim3In* sx = nullptr) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode != kPsFuse, kSim3 = kMode == kPsSim3;
+    constexpr bool kRagged = kSim3 || kMode == kPsFkf, kBlocked = kMode == kPsScw || kMode == kPsFkf;
     if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
     if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
     if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
         throw Error(ORBFE_EINVAL, "th and eps must be finite and eps not negative");
     int64_t n_items = 0;
-    if constexpr (kSim3) {
+    if constexpr (kRagged) {
         if (sx->n < 0) throw Error(ORBFE_EINVAL, "bad argument");
         if (sx->n == 0) return;
         if (!sx->off) throw Error(ORBFE_EINVAL, "null argument");
@@ -501,11 +561,11 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": srch_off must not decrease");
         n_items = sx->off[sx->n];
         if (n_items == 0) return;
-        if (!sx->f64 || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
+        if ((kSim3 && !sx->f64) || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
         for (int32_t q = 0; q < sx->n; ++q) {
             if (sx->kf[q] < 0 || sx->kf[q] >= n_kf)
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the target is outside the keyframes");
-            if (!all_finite(sx->f64 + (int64_t)q * ORBFE_SIM3_F64, ORBFE_SIM3_F64))
+            if (kSim3 && !all_finite(sx->f64 + (int64_t)q * ORBFE_SIM3_F64, ORBFE_SIM3_F64))
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": a scalar is not finite");
         }
         for (int64_t i = 0; i < n_items; ++i)
@@ -517,7 +577,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale ||
         (!kScw && !inv_sigma2) || !pt_f64 || !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
         throw Error(ORBFE_EINVAL, "null argument");
-    if (!kSim3 && out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
+    if (!kRagged && out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
     if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
         throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
     for (int32_t k = 0; k < n_kf; ++k)
@@ -561,7 +621,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
         }
     }
-    if constexpr (kSim3) {
+    if constexpr (kRagged) {
         for (int64_t i = 0; i < n_pts; ++i)  // slots 3-5, the normal, are not read
             if (!(all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64, 3) && all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64 + 6, 3)))
                 throw Error(ORBFE_EINVAL, "a point scalar is not finite");
@@ -570,16 +630,16 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     }
     // the outputs: a row of out_stride per keyframe, or flat over the items
     const size_t nk = (size_t)n_kf, np = (size_t)n_pts, os = (size_t)out_stride;
-    const size_t n_out = kSim3 ? (size_t)n_items : nk * os;
+    const size_t n_out = kRagged ? (size_t)n_items : nk * os;
     [[maybe_unused]] size_t ns = 0, n_chunk = 0;
     const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
                  nl = (size_t)lvl_off[n_kf];
     // what only one variant stages has no room in the other's buffers
-    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kMode == kPsScw ? pad16(n) : 0;
-    const bool has_blocked = kMode == kPsScw && blocked != nullptr && n > 0;
+    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kBlocked ? pad16(n) : 0;
+    const bool has_blocked = kBlocked && blocked != nullptr && n > 0;
     Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
-    if constexpr (kSim3) {
+    if constexpr (kRagged) {
         // no workgroup straddles two searches, and an empty search gets none
         ns = (size_t)sx->n;
         m.h_chunk.clear();
@@ -597,9 +657,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     hipStream_t s = m.stream;
     // descriptors are read as uint4: both blocks start on 16 bytes
     m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + n_blk + n_out);
-    m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 + ns * ORBFE_SIM3_F64);
-    m.d_i64.ensure(4 * (nk + 1) + (kSim3 ? ns + 1 + 2 * n_chunk : 0));
-    m.d_i32.ensure(3 * nk + n + nc + ni + (kSim3 ? ns + n_out : 0) + 2 * n_out);
+    m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 +
+                   (kSim3 ? ns * ORBFE_SIM3_F64 : 0));
+    m.d_i64.ensure(4 * (nk + 1) + (kRagged ? ns + 1 + 2 * n_chunk : 0));
+    m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + 2 * n_out);
     uint8_t* d_desc = m.d_u8.p;
     uint8_t* d_pdesc = d_desc + pad16(n * 32);
     uint8_t* d_blk = d_pdesc + pad16(np * 32);
@@ -623,7 +684,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     int32_t* d_cidx = d_coff + nc;
     [[maybe_unused]] int32_t* d_skf = d_cidx + ni;
     [[maybe_unused]] int32_t* d_item = d_skf + ns;
-    int32_t* d_bi = kSim3 ? d_item + n_out : d_cidx + ni;
+    int32_t* d_bi = kRagged ? d_item + n_out : d_cidx + ni;
     int32_t* d_bd = d_bi + n_out;
     auto up = [&](void* dst, const void* src, size_t bytes) {
         if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
@@ -646,13 +707,13 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     up(d_coff, cell_off, nc * sizeof(int32_t));
     up(d_cidx, cell_idx, ni * sizeof(int32_t));
     [[maybe_unused]] PsSim3 dsx{};
-    if constexpr (kSim3) {
-        up(d_sx, sx->f64, ns * ORBFE_SIM3_F64 * sizeof(double));
+    if constexpr (kRagged) {
+        if constexpr (kSim3) up(d_sx, sx->f64, ns * ORBFE_SIM3_F64 * sizeof(double));
         up(d_soff, sx->off, (ns + 1) * sizeof(int64_t));
         up(d_chunk, m.h_chunk.data(), 2 * n_chunk * sizeof(int64_t));
         up(d_skf, sx->kf, ns * sizeof(int32_t));
         up(d_item, sx->item_pt, n_out * sizeof(int32_t));
-        dsx = PsSim3{d_sx, d_skf, d_soff, d_item, d_chunk};
+        dsx = PsSim3{kSim3 ? d_sx : nullptr, d_skf, d_soff, d_item, d_chunk};
     }
     PsKfs kf{};
     kf.f64 = d_kf;
@@ -673,8 +734,9 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     const PsPts pt{d_pt, d_pdesc, n_pts};
     const PsOut d{d_bi, d_bd, d_st, out_stride};
     HIPCK(hipEventRecord(m.ev[0], s));
-    if constexpr (kSim3) {
-        hipLaunchKernelGGL(k_sim3_search, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx);
+    if constexpr (kRagged) {
+        constexpr auto kernel = kSim3 ? k_sim3_search : k_fkf_search;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx);
     } else {
         const unsigned chunks = (unsigned)((np + kPsChunk - 1) / kPsChunk);
         constexpr auto kernel = kFuse ? k_fuse_search : k_scw_search;
@@ -690,7 +752,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, n_out, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
-    if constexpr (kSim3) {  // every item was written
+    if constexpr (kRagged) {  // every item was written
         std::memcpy(out->best_idx, m.h_i32.data(), n_out * sizeof(int32_t));
         std::memcpy(out->best_dist, m.h_i32.data() + n_out, n_out * sizeof(int32_t));
         std::memcpy(out->status, m.h_st.data(), n_out);
@@ -761,6 +823,23 @@ int orbfe_sim3_search(const double* kf_f64, const int32_t* kf_i32, const int64_t
 
 int orbfe_sim3_search_last_ms(float* ms) {
     return guarded([&] { last_ms<kPsSim3>(ms); });
+}
+
+int orbfe_fkf_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                     const int32_t* octave, const uint8_t* desc32, const uint8_t* blocked, const int64_t* cell_at,
+                     const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx, const int64_t* lvl_off,
+                     const double* scale, int32_t n_kf, const double* pt_f64, const uint8_t* pt_desc32, int64_t n_pts,
+                     const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt,
+                     double th, double eps, const orbfe_fkf_out* out) {
+    return guarded([&] {
+        const Sim3In sx{nullptr, srch_kf, srch_off, n_srch, item_pt};
+        search<kPsFkf>(kf_f64, kf_i32, off, xy, octave, nullptr, desc32, blocked, cell_at, cell_off, idx_at, cell_idx,
+                       lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, 0, &sx);
+    });
+}
+
+int orbfe_fkf_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<kPsFkf>(ms); });
 }
 
 }  // extern "C"

@@ -34,7 +34,9 @@ single search.  fuse_pkf_mp_many (k_fuse_search) does the same for LocalMapping'
 the search of every (keyframe, point), then the matches applied on the host in the reference's order.
 fuse_kf_scw_mp_many and search_by_projection_ckf_scw_mp (k_scw_search) do it for LoopClosing's two Sim3 searches,
 and search_by_sim3 / search_by_sim3_many (k_sim3_search) for its mutual search: both directions of every candidate
-pair in one launch, nothing to replay in order.
+pair in one launch, nothing to replay in order.  search_by_projection_f_kf_f / _f_kf_f_many (k_fkf_search) do it
+for Tracking.relocalization's search into a frame, which assigns into the frame it searches: one launch, then the
+assignments replayed in list order.
 """
 from __future__ import annotations
 
@@ -610,10 +612,11 @@ def _tri_epipole(ex, ey, f2):
 
 
 def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off, scale,
-                   pt_f64, pt_desc, th, eps, u_right=None, inv_sigma2=None, blocked=None, sim3=None) -> dict:
-    """fuse_search_arrays (fuse, with u_right and inv_sigma2), scw_search_arrays (not fuse, with blocked or None)
-    and sim3_search_arrays (not fuse, with sim3 = (srch_f64, srch_kf, srch_off, item_pt)): the conversion, the
-    length checks, the outputs and the call."""
+                   pt_f64, pt_desc, th, eps, u_right=None, inv_sigma2=None, blocked=None, sim3=None, fkf=None) -> dict:
+    """fuse_search_arrays (fuse, with u_right and inv_sigma2), scw_search_arrays (not fuse, with blocked or None),
+    sim3_search_arrays (not fuse, with sim3 = (srch_f64, srch_kf, srch_off, item_pt)) and fkf_search_arrays (not
+    fuse, with blocked or None and fkf = (srch_kf, srch_off, item_pt)): the conversion, the length checks, the
+    outputs and the call."""
     def arr(a, dt):
         return None if a is None else np.ascontiguousarray(a, dt)
     kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
@@ -641,10 +644,14 @@ def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_of
         if blocked is not None and blocked.size < n:
             raise ValueError("blocked does not have one byte per feature")
     grid = (ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale))
-    if sim3 is not None:
-        srch_f64 = np.ascontiguousarray(sim3[0], np.float64).reshape(-1, _lib.ORBFE_SIM3_F64)
+    if sim3 is not None or fkf is not None:
+        if sim3 is not None:
+            srch_f64 = np.ascontiguousarray(sim3[0], np.float64).reshape(-1, _lib.ORBFE_SIM3_F64)
+            n_srch = len(srch_f64)
+        else:
+            sim3 = (None,) + tuple(fkf)
+            n_srch = 0 if fkf[0] is None else int(np.size(fkf[0]))
         srch_kf, srch_off, item_pt = arr(sim3[1], np.int32), arr(sim3[2], np.int64), arr(sim3[3], np.int32)
-        n_srch = len(srch_f64)
         if srch_kf is None or srch_off is None or srch_kf.size != n_srch or srch_off.size != n_srch + 1:
             raise ValueError("srch_kf / srch_off do not cover the searches")
         n_items = int(srch_off[-1])
@@ -652,6 +659,12 @@ def _search_arrays(fuse, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_of
             raise ValueError("item_pt is shorter than srch_off says")
         n_items = max(n_items, 0)
         bi, bd, st = np.full(n_items, -1, np.int32), np.full(n_items, -1, np.int32), np.zeros(n_items, np.uint8)
+        if fkf is not None:
+            out = _lib.FkfOut(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
+            call("orbfe_fkf_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(desc), ptr(blocked),
+                 *grid, n_kf, ptr(pt_f64), ptr(pt_desc), n_pts, ptr(srch_kf), ptr(srch_off), n_srch, ptr(item_pt),
+                 float(th), float(eps), C.byref(out))
+            return dict(best_idx=bi, best_dist=bd, status=st)
         out = _lib.Sim3Out(best_idx=bi.ctypes.data, best_dist=bd.ctypes.data, status=st.ctypes.data)
         call("orbfe_sim3_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(desc), *grid, n_kf,
              ptr(pt_f64), ptr(pt_desc), n_pts, ptr(srch_f64), ptr(srch_kf), ptr(srch_off), n_srch, ptr(item_pt),
@@ -709,6 +722,20 @@ def sim3_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off,
                           scale, pt_f64, pt_desc, th, eps, sim3=(srch_f64, srch_kf, srch_off, item_pt))
 
 
+def fkf_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                      scale, pt_f64, pt_desc, srch_kf, srch_off, item_pt, th, eps) -> dict:
+    """orbfe_fkf_search (k_fkf_search, include/orbfe.h): the search half of ORBMatcher.search_by_projection_f_kf_f
+    (ORBMatcher.py:936-983, with Frame.get_features_in_area, Frame.py:373-416) for many (frame, map point list)
+    searches in one launch.  The target arrays are scw_search_arrays' with a Frame in each block (the pose slots
+    from mTcw and Ow = -Rcw^T tcw, the grid FRAME_GRID_COLS x FRAME_GRID_ROWS), blocked included: None, or one byte
+    per feature, non-zero for a feature whose map point slot is taken.  pt_f64 (P, 9) / pt_desc (P, 32) are one
+    shared point table (the normal is not read).  Search s has the target srch_kf[s] and the items
+    [srch_off[s], srch_off[s + 1]) of item_pt, rows of the point table.  Returns best_idx, best_dist int32 (-1: no
+    candidate) and status uint8 (ORBFE_FUSE_MARGINAL), flat over the items."""
+    return _search_arrays(False, kf_f64, kf_i32, off, xy, octave, desc, cell_at, cell_off, idx_at, cell_idx, lvl_off,
+                          scale, pt_f64, pt_desc, th, eps, blocked=blocked, fkf=(srch_kf, srch_off, item_pt))
+
+
 # eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
 # float32 (2^-24 is its unit roundoff) and the 2^-48 class of k_tri_match for float64
 FUSE_EPS_F32 = 2.0 ** -23
@@ -732,9 +759,10 @@ def _pose_part(a, shape):
     return a.astype(np.float64).reshape(-1).tolist(), a.dtype == _F32_DT
 
 
-def _fuse_static(kf):
+def _fuse_static(kf, dims=None):
     """(xy, octave, desc, cell_off, cell_idx) of a keyframe, cached while mvKeysUn, mDescriptors and mGrid are the
-    same objects; None for what the arrays cannot express."""
+    same objects; None for what the arrays cannot express.  dims: the grid's (columns, rows) where they are not
+    mnGridCols / mnGridRows (a Frame's FRAME_GRID_COLS / FRAME_GRID_ROWS)."""
     kps, descs, grid = kf.mvKeysUn, kf.mDescriptors, kf.mGrid
     try:
         ent = _fuse_cache.get(kf)
@@ -743,7 +771,7 @@ def _fuse_static(kf):
     if ent is not None and ent[0] is kps and ent[1] is descs and ent[2] is grid and ent[3] == len(kps):
         return ent[4]
     n = len(kps)
-    cols, rows = kf.mnGridCols, kf.mnGridRows
+    cols, rows = dims if dims is not None else (kf.mnGridCols, kf.mnGridRows)
     if not (type(cols) in _INT_SET and type(rows) in _INT_SET and 0 < cols <= 4096 and 0 < rows <= 4096):
         return None
     if n > _lib.ORBFE_BOW_MAX_FRAME:
@@ -832,11 +860,64 @@ def _fuse_frame(kf):
     return f
 
 
-def _fuse_point(pMP):
+def _fkf_frame(F):
+    """Array form of a Frame for k_fkf_search, with the surface search_by_projection_f_kf_f and
+    Frame.get_features_in_area read (Frame.py): the _FuseFrame of _fuse_frame without right coordinates and inverse
+    sigma squares, the grid FRAME_GRID_COLS x FRAME_GRID_ROWS, the bf slot 0.0 (not read), the pose slots from mTcw
+    and Ow = -Rcw^T tcw by the reference's expression, kept in f.pose as (Rcw, tcw, Ow).  None when the arrays cannot
+    express the frame (the caller then takes the host body): an attribute of that surface is missing, intrinsics or
+    grid parameters are not plain doubles, mTcw is not a finite 4 x 4 float32 / float64 array or the centre it
+    gives is not finite, and what _fuse_static and _fuse_frame refuse in a keyframe's features, grid and scale
+    table."""
+    try:
+        sc = (F.fx, F.fy, F.cx, F.cy)
+        gr = (F.mnMinX, F.mnMaxX, F.mnMinY, F.mnMaxY, F.mfGridElementWidthInv, F.mfGridElementHeightInv,
+              F.mfLogScaleFactor)
+        dims, levels, sf, T = (F.FRAME_GRID_COLS, F.FRAME_GRID_ROWS), F.mnScaleLevels, F.mvScaleFactors, F.mTcw
+    except AttributeError:
+        return None
+    if not (set(map(type, sc)) <= _F64_SET and set(map(type, gr)) <= _F64_SET):
+        return None
+    if type(levels) not in _INT_SET or levels <= 0:
+        return None
+    if not (type(T) is np.ndarray and T.shape == (4, 4) and T.dtype in _POSE_DT and bool(np.isfinite(T).all())):
+        return None
+    Rcw, tcw = T[:3, :3], T[:3, 3:4]
+    with np.errstate(all="ignore"):
+        Ow = -np.dot(Rcw.T, tcw)
+    R, t, O = _pose_part(Rcw, (3, 3)), _pose_part(tcw, (3, 1)), _pose_part(Ow, (3, 1))
+    if R is None or t is None or O is None:
+        return None
+    st = _fuse_static(F, dims)
+    if st is None:
+        return None
+    xy, octave, desc, cell_off, cell_idx = st
+    if len(cell_off) != dims[0] * dims[1] + 1:  # cached for the same mGrid under another FRAME_GRID_COLS / ROWS
+        return None
+    if len(sf) < levels:
+        return None
+    sf = list(sf[:levels])
+    if not set(map(type, sf)) <= _F64_SET:
+        return None
+    f64, scale = np.array(list(sc) + [0.0] + R[0] + t[0] + O[0] + list(gr), np.float64), np.array(sf, np.float64)
+    if not (np.isfinite(f64).all() and np.isfinite(scale).all()):
+        return None
+    if len(xy) and (int(octave.min()) < 0 or int(octave.max()) >= levels):
+        return None
+    f = _FuseFrame()
+    f.f64, f.i32 = f64, np.array([dims[0], dims[1], levels], np.int32)
+    f.xy, f.octave, f.desc, f.cell_off, f.cell_idx, f.scale = xy, octave, desc, cell_off, cell_idx, scale
+    f.f32, f.pose = T.dtype == _F32_DT, (Rcw, tcw, Ow)
+    return f
+
+
+def _fuse_point(pMP, normal=True):
     """(9 doubles, descriptor row, any float32) of a map point for k_fuse_search, or None when the arrays cannot
     express it: a position or normal that is not a finite (3, 1) float32 / float64 array, distances that are not
-    plain doubles, a descriptor that is not 32 bytes of uint8."""
-    p, nrm = _pose_part(pMP.get_world_pos(), (3, 1)), _pose_part(pMP.get_normal(), (3, 1))
+    plain doubles, a descriptor that is not 32 bytes of uint8.  normal False (k_fkf_search, whose reference never
+    asks for it): get_normal is not called and the slots hold zeros."""
+    p = _pose_part(pMP.get_world_pos(), (3, 1))
+    nrm = _pose_part(pMP.get_normal(), (3, 1)) if normal else ([0.0, 0.0, 0.0], False)
     if p is None or nrm is None:
         return None
     d3 = (pMP.get_min_distance_invariance(), pMP.get_max_distance_invariance(), pMP.mfMaxDistance)
@@ -1590,15 +1671,15 @@ class ORBMatcher:
         return f, (Rcw, tcw, Ow)
 
     @staticmethod
-    def _search_points(vpPoints, skip):
+    def _search_points(vpPoints, skip, normal=True):
         """The points once: (slot per list position, rows, descriptor rows, any float32).  slot >= 0 is the row sent
-        to the device, -1 not expressible (_fuse_point), -2 skipped by skip(pMP)."""
+        to the device, -1 not expressible (_fuse_point, with its normal), -2 skipped by skip(pMP)."""
         slot, rows, descs, f32 = [], [], [], False
         for pMP in vpPoints:
             if skip(pMP):
                 slot.append(-2)
                 continue
-            pt = _fuse_point(pMP)
+            pt = _fuse_point(pMP, normal)
             if pt is None:
                 slot.append(-1)
                 continue
@@ -1609,10 +1690,10 @@ class ORBMatcher:
         return slot, rows, descs, f32
 
     @staticmethod
-    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None):
+    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None, fkf=None):
         """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse), of
-        scw_search_arrays (with blocked) or of sim3_search_arrays (with sim3 = (srch_f64, srch_kf, srch_off,
-        item_pt))."""
+        scw_search_arrays (with blocked), of sim3_search_arrays (with sim3 = (srch_f64, srch_kf, srch_off,
+        item_pt)) or of fkf_search_arrays (with blocked and fkf = (srch_kf, srch_off, item_pt))."""
         def offs(lens):
             o = np.zeros(len(fr) + 1, np.int64)
             np.cumsum(lens, out=o[1:])
@@ -1627,6 +1708,8 @@ class ORBMatcher:
             return fuse_search_arrays(*head, cat("u_right"), cat("desc"), *grid, cat("inv_sigma2"), *pts)
         if sim3 is not None:
             return sim3_search_arrays(*head, cat("desc"), *grid, *pts[:2], *sim3, *pts[2:])
+        if fkf is not None:
+            return fkf_search_arrays(*head, cat("desc"), blocked, *grid, *pts[:2], *fkf, *pts[2:])
         return scw_search_arrays(*head, cat("desc"), blocked, *grid, *pts)
 
     def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
@@ -2425,8 +2508,174 @@ class ORBMatcher:
                 n_matches += 1
         return n_matches, vpMatched
 
+    @staticmethod
+    def _fkf_job(CurrentFrame, th, ORBdist):
+        """_fkf_frame(CurrentFrame) when one search of search_by_projection_f_kf_f can run on the device, else
+        None: see the conditions there."""
+        if not (type(th) in _TH_SET and np.isfinite(th) and type(ORBdist) in (int, float) and ORBdist < 256):
+            return None
+        f = _fkf_frame(CurrentFrame)
+        if f is None:
+            return None
+        mvp = CurrentFrame.mvpMapPoints
+        if not (isinstance(mvp, list) and len(mvp) == len(f.xy) == CurrentFrame.N):
+            return None
+        return f
+
+    def _fkf_one(self, CurrentFrame, pMP, Rcw, tcw, Ow, th):
+        """(bestDist, bestIdx2) of one point against the current CurrentFrame.mvpMapPoints with the reference's own
+        expressions on the objects (ORBMatcher.py:939-983), raising what they raise; the few distances are host
+        popcounts."""
+        with np.errstate(all="ignore"):
+            x3Dw = pMP.get_world_pos()
+            x3Dc = np.dot(Rcw, x3Dw) + tcw
+            xc = x3Dc[0]
+            yc = x3Dc[1]
+            invzc = 1.0 / x3Dc[2]
+            u = CurrentFrame.fx * xc * invzc + CurrentFrame.cx
+            v = CurrentFrame.fy * yc * invzc + CurrentFrame.cy
+            if u < CurrentFrame.mnMinX or u > CurrentFrame.mnMaxX or v < CurrentFrame.mnMinY or v > CurrentFrame.mnMaxY:
+                return 256, -1
+            PO = x3Dw - Ow
+            dist3D = np.linalg.norm(PO)
+            maxDistance = pMP.get_max_distance_invariance()
+            minDistance = pMP.get_min_distance_invariance()
+            if dist3D < minDistance or dist3D > maxDistance:
+                return 256, -1
+            lvl = pMP.predict_scale(dist3D, CurrentFrame)
+            vIndices2 = CurrentFrame.get_features_in_area(u, v, th * CurrentFrame.mvScaleFactors[lvl], lvl - 1, lvl + 1)
+        best_dist, best_idx2 = 256, -1
+        if not vIndices2:
+            return best_dist, best_idx2
+        dMP = pMP.get_descriptor()
+        for i2 in vIndices2:
+            if CurrentFrame.mvpMapPoints[i2]:
+                continue
+            dist = descriptor_distance(dMP, CurrentFrame.mDescriptors[i2])
+            if dist < best_dist:
+                best_dist = dist
+                best_idx2 = i2
+        return best_dist, best_idx2
+
+    def _fkf_jobs(self, jobs, th, ORBdist):
+        """search_by_projection_f_kf_f for every (CurrentFrame, pKF, sAlreadyFound, _fkf_frame(CurrentFrame)) of
+        jobs, whose frames are distinct objects with distinct mvpMapPoints lists, from one k_fkf_search launch of
+        one search per job: the match counts.  Per job in the reference's order: the prefilter in list order, the
+        blocked bytes (the truth value of every mvpMapPoints slot) taken once, then after the launch the replay in
+        list order (see search_by_projection_f_kf_f)."""
+        frames, rows, descs, f32, preps = [], [], [], False, []
+        srch_off, item_pt, blocked = [0], [], []
+        for CurrentFrame, pKF, sAlreadyFound, f in jobs:
+            vpMPs = pKF.get_map_point_matches()
+            slot, rows_j, descs_j, p32 = self._search_points(
+                vpMPs, lambda p: not (p and not p.is_bad() and p not in sAlreadyFound), normal=False)
+            slot = np.array(slot, np.int64).reshape(-1)
+            sent = np.flatnonzero(slot >= 0)
+            item_pt.append(slot[sent] + len(rows))
+            srch_off.append(srch_off[-1] + len(sent))
+            rows += rows_j
+            descs += descs_j
+            f32 = f32 or p32 or f.f32
+            mvp = CurrentFrame.mvpMapPoints
+            blocked.append(np.fromiter((bool(m) for m in mvp), np.uint8, count=len(mvp)))
+            frames.append(f)
+            preps.append((vpMPs, slot, sent))
+        if srch_off[-1]:
+            res = self._search_launch(frames, rows, descs, th, f32, blocked=np.concatenate(blocked), fkf=(
+                np.arange(len(jobs), dtype=np.int32), np.array(srch_off, np.int64),
+                np.concatenate(item_pt).astype(np.int32)))
+            bi_all, bd_all, st_all = res["best_idx"], res["best_dist"], res["status"]
+        out = []
+        factor = 1.0 / HISTO_LENGTH
+        for q, ((CurrentFrame, pKF, _, f), (vpMPs, slot, sent)) in enumerate(zip(jobs, preps)):
+            Rcw, tcw, Ow = f.pose
+            mvp = CurrentFrame.mvpMapPoints
+            rot_hist = [[] for _ in range(HISTO_LENGTH)]
+            todo = np.flatnonzero(slot == -1)
+            at = {}
+            if len(sent):
+                seg = slice(srch_off[q], srch_off[q + 1])
+                bi, bd, st = bi_all[seg], bd_all[seg], st_all[seg]
+                # what is left of a point's candidates is never closer than its best: an unmarked item above
+                # ORBdist, or without a candidate, assigns nothing whatever was taken meanwhile
+                live = (st != 0) | ((bi >= 0) & (bd <= ORBdist))
+                todo = np.sort(np.concatenate([todo, sent[live]]))
+                at = dict(zip(sent[live].tolist(), zip(bi[live].tolist(), bd[live].tolist(), st[live].tolist())))
+            n_matches = 0
+            for i in todo.tolist():
+                pMP = vpMPs[i]
+                dev = at.get(i)
+                if dev is not None and not dev[2] and not mvp[dev[0]]:
+                    best_idx2, best_dist = dev[0], dev[1]
+                else:
+                    best_dist, best_idx2 = self._fkf_one(CurrentFrame, pMP, Rcw, tcw, Ow, th)
+                if best_dist <= ORBdist:
+                    mvp[best_idx2] = pMP
+                    n_matches += 1
+                    if self.mbCheckOrientation:
+                        rot = pKF.mvKeysUn[i].angle - CurrentFrame.mvKeysUn[best_idx2].angle
+                        if rot < 0.0:
+                            rot += 360.0
+                        b = round(rot * factor)
+                        if b == HISTO_LENGTH:
+                            b = 0
+                        assert 0 <= b < HISTO_LENGTH
+                        rot_hist[b].append(best_idx2)
+            if self.mbCheckOrientation:
+                n_matches -= self._reject_by_rotation(rot_hist, lambda i, mvp=mvp: mvp.__setitem__(i, None))
+            out.append(n_matches)
+        return out
+
     # ORBMatcher.py:924-1008
     def search_by_projection_f_kf_f(self, CurrentFrame, pKF, sAlreadyFound, th, ORBdist):
+        """Tracking.relocalization's search (Tracking.py:661-763) from one k_fkf_search launch: the prefilter in list
+        order (pMP and not pMP.is_bad() and pMP not in sAlreadyFound), blocked[i] = bool(mvpMapPoints[i]) taken once,
+        then the replay in list order.  An item that came back ORBFE_FUSE_MARGINAL, or whose point the arrays cannot
+        express, or whose best feature an earlier item of this call has taken meanwhile, is redone alone against the
+        current mvpMapPoints with the reference's expressions (_fkf_one, raising what they raise); otherwise the
+        device's answer stands and is assigned when best_dist <= ORBdist.  Taking candidates away never makes a
+        remaining one closer, so an unmarked item above ORBdist needs no redo.  The rotation histogram and its
+        rejection follow as in the reference.  The host body (_fkf_host) runs instead when the HIP runtime sees no
+        device (its only device work is _batched, the seam the host-logic tests replace), when th is not a plain
+        finite number, when ORBdist is not a plain int / float below 256 (from 256 on the reference assigns to index
+        -1 once every candidate is taken), when CurrentFrame.mvpMapPoints is not a list of N entries, or when
+        _fkf_frame refuses the frame."""
+        if _lib.device_present():
+            f = self._fkf_job(CurrentFrame, th, ORBdist)
+            if f is not None:
+                return self._fkf_jobs([(CurrentFrame, pKF, sAlreadyFound, f)], th, ORBdist)[0]
+        return self._fkf_host(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+
+    def search_by_projection_f_kf_f_many(self, frames, kfs, sAlreadyFounds, th, ORBdist):
+        """What this list holds, value for value and leaving every frame's mvpMapPoints as the loop leaves it, from
+        one k_fkf_search launch of one search per frame:
+
+            [self.search_by_projection_f_kf_f(f, kf, s, th, ORBdist)
+             for f, kf, s in zip(frames, kfs, sAlreadyFounds)]
+
+        (several lost frames relocalising at once, or one frame against several keyframes after a host-side copy
+        of it per keyframe).  Each frame is packed once.  A frame that cannot take the device path (see
+        search_by_projection_f_kf_f) takes the single call at its place.  The loop itself runs when a frame object,
+        or an mvpMapPoints list, occurs twice (its second search would read what the first assigned) and where the
+        HIP runtime sees no device."""
+        cols = [list(c) for c in (frames, kfs, sAlreadyFounds)]
+        jobs = list(zip(*cols))
+        if any(len(c) != len(jobs) for c in cols):
+            raise ValueError("one keyframe and one sAlreadyFound per frame")
+        res = [None] * len(jobs)
+        distinct = len({id(j[0]) for j in jobs}) == len(jobs) == len({id(getattr(j[0], "mvpMapPoints", j[0]))
+                                                                     for j in jobs})
+        if jobs and distinct and _lib.device_present():
+            packed = [self._fkf_job(j[0], th, ORBdist) for j in jobs]
+            take = [k for k, f in enumerate(packed) if f is not None]
+            if take:
+                for k, n in zip(take, self._fkf_jobs([jobs[k] + (packed[k],) for k in take], th, ORBdist)):
+                    res[k] = n
+        return [self.search_by_projection_f_kf_f(*j, th, ORBdist) if r is None else r for j, r in zip(jobs, res)]
+
+    def _fkf_host(self, CurrentFrame, pKF, sAlreadyFound, th, ORBdist):
+        """search_by_projection_f_kf_f on the host, point by point (only the Hamming distances run on the device):
+        the fallback of the public method."""
         Rcw = CurrentFrame.mTcw[:3, :3]
         tcw = CurrentFrame.mTcw[:3, 3:4]
         Ow = -np.dot(Rcw.T, tcw)

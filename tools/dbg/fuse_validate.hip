@@ -1,12 +1,12 @@
 // fuse_validate.hip — host-side sanitizer check of the argument validation of orbfe_fuse_search,
-// orbfe_scw_search and orbfe_sim3_search.
+// orbfe_scw_search, orbfe_sim3_search and orbfe_fkf_search.
 //
 // A program of its own: it links orbfe_fuse.hip alone and calls the entries only with arguments that the validation
 // refuses (or with nothing to do), all of which return before any device call, so it runs on a machine without a
 // GPU.  What orbfe_scw_search accepts where orbfe_fuse_search refuses (a null blocked, anything in slot 4 of the
 // keyframe scalars) would reach the device on its own, so each is paired with one later refusal and the message must
 // be that later one's; likewise for what orbfe_sim3_search accepts (anything in slots 0-19 of a keyframe's scalars
-// and in the normal of a point).  Build and run with tools/dbg/fuse_validate_asan.sh (host code under
+// and in the normal of a point) and orbfe_fkf_search (a null blocked, slot 4, the normal).  Build and run with tools/dbg/fuse_validate_asan.sh (host code under
 // -fsanitize=address,undefined).
 #include <cmath>
 #include <cstdint>
@@ -261,6 +261,96 @@ void sim3_refusals() {
     }
 }
 
+// orbfe_fkf_search: Sim3Input without the search scalars, with blocked
+struct FkfInput : Sim3Input {
+    int runf() {
+        orbfe_fkf_out o{p(bi3), p(bd3), p(st3)};
+        return orbfe_fkf_search(p(kf), p(ki), p(off), p(xy), p(octave), p(desc), p(blocked), p(cell_at), p(cell_off),
+                                p(idx_at), p(cell_idx), p(lvl_off), p(scale), n_kf, p(pt), p(pdesc), n_pts, p(skf),
+                                p(soff), n_srch, p(item), th, eps, null_out ? nullptr : &o);
+    }
+};
+
+void expectf(const char* what, int want, const std::function<void(FkfInput&)>& breakit, const char* message = "") {
+    FkfInput in;
+    breakit(in);
+    orbfe::g_err.clear();
+    const int rc = in.runf();
+    ++checks;
+    if (rc != want || !in.untouched3() || orbfe::g_err.find(message) == std::string::npos) {
+        std::printf("FAIL fkf %s: rc %d (want %d), outputs %s, message: %s (want: %s)\n", what, rc, want,
+                    in.untouched3() ? "untouched" : "WRITTEN", orbfe::g_err.c_str(), message);
+        ++failures;
+    }
+}
+
+void fkf_refusals() {
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    const int E = ORBFE_EINVAL;
+    expectf("negative keyframe count", E, [](FkfInput& i) { i.n_kf = -1; });
+    expectf("negative point count", E, [](FkfInput& i) { i.n_pts = -1; });
+    expectf("negative search count", E, [](FkfInput& i) { i.n_srch = -1; });
+    expectf("too many keyframes", E, [](FkfInput& i) { i.n_kf = 65536; });
+    expectf("th nan", E, [&](FkfInput& i) { i.th = nan; });
+    expectf("eps negative", E, [](FkfInput& i) { i.eps = -1.0; });
+    expectf("no searches", ORBFE_OK, [](FkfInput& i) { i.n_srch = 0; });
+    expectf("no items", ORBFE_OK, [](FkfInput& i) { i.soff = {0, 0, 0, 0}; });
+    expectf("null out", E, [](FkfInput& i) { i.null_out = true; });
+#define NULLF(field) expectf("null " #field, E, [](FkfInput& i) { i.skip = i.field.data(); }, "null argument")
+    NULLF(kf);
+    NULLF(ki);
+    NULLF(off);
+    NULLF(xy);
+    NULLF(octave);
+    NULLF(desc);
+    NULLF(cell_at);
+    NULLF(cell_off);
+    NULLF(idx_at);
+    NULLF(cell_idx);
+    NULLF(lvl_off);
+    NULLF(scale);
+    NULLF(pt);
+    NULLF(pdesc);
+    NULLF(skf);
+    NULLF(soff);
+    NULLF(item);
+    NULLF(bi3);
+    NULLF(bd3);
+    NULLF(st3);
+    expectf("srch_off[0] not 0", E, [](FkfInput& i) { i.soff[0] = 1; }, "srch_off[0]");
+    expectf("srch_off decreases", E, [](FkfInput& i) { i.soff[2] = 1; }, "search 1");
+    expectf("target past the keyframes", E, [](FkfInput& i) { i.skf[2] = 1; }, "search 2");
+    expectf("target negative", E, [](FkfInput& i) { i.skf[0] = -1; }, "search 0");
+    expectf("item past the points", E, [](FkfInput& i) { i.item[2] = 2; }, "outside the point table");
+    expectf("item negative", E, [](FkfInput& i) { i.item[0] = -1; }, "outside the point table");
+    expectf("off[0] not 0", E, [](FkfInput& i) { i.off[0] = 1; });
+    expectf("frame above the cap", E, [](FkfInput& i) { i.off[1] = ORBFE_BOW_MAX_FRAME + 1; });
+    expectf("level count 0", E, [](FkfInput& i) { i.ki[2] = 0; });
+    expectf("grid entry past the features", E, [](FkfInput& i) { i.cell_idx[1] = 2; });
+    expectf("octave negative", E, [](FkfInput& i) { i.octave[0] = -1; });
+    expectf("coordinate inf", E, [&](FkfInput& i) { i.xy[3] = inf; });
+    expectf("scale nan", E, [&](FkfInput& i) { i.scale[1] = nan; });
+    for (int c = 0; c < ORBFE_FUSE_KF_F64; ++c) {
+        if (c == 4) continue;  // bf: not read, see below
+        expectf("frame scalar nan", E, [&](FkfInput& i) { i.kf[c] = c % 2 ? nan : -inf; }, "a scalar is not finite");
+    }
+    const char* later = "a point scalar is not finite";
+    for (int c = 0; c < 2 * ORBFE_FUSE_PT_F64; ++c) {
+        if (c % ORBFE_FUSE_PT_F64 >= 3 && c % ORBFE_FUSE_PT_F64 < 6) continue;  // the normal: not read, see below
+        expectf("point scalar nan", E, [&](FkfInput& i) { i.pt[c] = nan; }, later);
+    }
+    // accepted by the validation: the refusal is the later one, of the point scalar
+    expectf("null blocked goes on", E, [&](FkfInput& i) { i.skip = i.blocked.data(), i.pt[0] = nan; }, later);
+    expectf("bf nan goes on", E, [&](FkfInput& i) { i.kf[4] = nan, i.pt[0] = nan; }, later);
+    for (int c = 3; c < 6; ++c)
+        expectf("normal goes on", E, [&](FkfInput& i) { i.pt[c] = -inf, i.pt[ORBFE_FUSE_PT_F64] = nan; }, later);
+    float ms = -1.f;
+    if (orbfe_fkf_search_last_ms(nullptr) != E || orbfe_fkf_search_last_ms(&ms) != ORBFE_OK || ms != 0.f) {
+        std::printf("FAIL fkf last_ms\n");
+        ++failures;
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -269,6 +359,7 @@ int main() {
         refusals();
     }
     sim3_refusals();
+    fkf_refusals();
     std::printf("%d checks, %d failures\n", checks, failures);
     return failures ? 1 : 0;
 }

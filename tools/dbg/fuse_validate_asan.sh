@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds tools/dbg/fuse_validate.hip with orbfe_fuse.hip, host code under AddressSanitizer and UBSan, and runs it on
-# the CPU: every call of orbfe_fuse_search, orbfe_scw_search and orbfe_sim3_search returns from the argument validation, before any
-# device call.
+# the CPU: every call of orbfe_fuse_search, orbfe_scw_search, orbfe_sim3_search and orbfe_fkf_search returns from the
+# argument validation, before any device call.
 set -euo pipefail
 cd "$(dirname "$0")/../.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
