@@ -44,7 +44,7 @@ extern "C" {
                                * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out, and orbfe_scw_search,
                                * orbfe_scw_search_last_ms and orbfe_scw_out, and orbfe_sim3_search,
                                * orbfe_sim3_search_last_ms and orbfe_sim3_out, and orbfe_fkf_search,
-                               * orbfe_fkf_search_last_ms and orbfe_fkf_out */
+                               * orbfe_fkf_search_last_ms and orbfe_fkf_out, and orbfe_debug_detect_lanes */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -388,6 +388,13 @@ int orbfe_debug_cascade_profile(orbfe_handle h, int64_t* marks, int64_t n_marks,
  * one-pass path (both thresholds over the minTh queue), stats[2] = cells that fell back to minTh
  * (ORBextractor.cpp:811-815) on the two-queue path.  Development aid; results are unchanged. */
 int orbfe_debug_detect_stats(orbfe_handle h, int64_t* stats);
+/* orbfe_debug_detect_lanes: the same re-run in both launch shapes (four cells per wave, then one; ORBFE_ESTATE
+ * should their counters differ), the first n (1 .. 7) words of: the three of orbfe_debug_detect_stats, then, on the
+ * two-queue path, stats[3] = cells whose last iniTh M step carried minTh-queue entries in its idle lanes,
+ * stats[4] = entries carried so, stats[5] = M steps the minTh fallbacks ran (ceil((|B| - carried) / 64) per fallback
+ * cell); and for every cell with minTh < iniTh stats[6] = pre-test halves whose iniTh-queue emission was skipped
+ * for having no iniTh pair.  Development aid; results are unchanged. */
+int orbfe_debug_detect_lanes(orbfe_handle h, int64_t* stats, int32_t n);
 
 /* DistributeOctTree implementation (ORBextractor.cpp:539-762; results are identical): 0 = automatic
  * (k_octree_bins, or the per-candidate k_octree when the bins' LDS carve would exceed 150 KiB), 1 = always

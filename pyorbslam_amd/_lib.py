@@ -170,6 +170,7 @@ SIGNATURES = {
     "orbfe_get_octree_kernel": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
     "orbfe_get_stereo_bucket_kernel": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "orbfe_debug_detect_stats": [C.c_void_p, C.POINTER(C.c_int64)],
+    "orbfe_debug_detect_lanes": [C.c_void_p, C.POINTER(C.c_int64), C.c_int32],
     "orbfe_vocab_load_text": [C.c_char_p, C.POINTER(C.c_void_p)],
     "orbfe_vocab_create": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_void_p)],

@@ -2138,21 +2138,43 @@ int orbfe_get_stereo_bucket_kernel(orbfe_handle h, int32_t n_images, int32_t* fu
     });
 }
 
+// k_detect's debug counters (the ST instantiations): the three words of orbfe_debug_detect_stats, then the four of
+// orbfe_debug_detect_lanes
+constexpr int kDetectStats = 7;
+// cells_per_wave: 0 = the batch's own launch shape, 4 / 1 forced
+static void detect_counters(orbfe_ctx* h, int cells_per_wave, int* v) {
+    if (h->last_images <= 0 || !h->last_in) throw Error(ORBFE_ESTATE, "run a batch first");
+    const Geo& g = h->geo;
+    DevBuf<int> d;
+    d.ensure(kDetectStats);
+    HIPCK(hipMemset(d.p, 0, kDetectStats * sizeof(int)));
+    if (g.ncells > 0)
+        HIPCK(launch_detect(g, h->d_cells.p, h->last_in, h->last_pitch, h->d_ws.p, h->d_cell_count.p, h->d_slots.p,
+                            h->last_images, h->last_stream, cells_per_wave, d.p));
+    HIPCK(hipStreamSynchronize(h->last_stream));
+    HIPCK(hipMemcpy(v, d.p, kDetectStats * sizeof(int), hipMemcpyDeviceToHost));
+}
+
 int orbfe_debug_detect_stats(orbfe_handle h, int64_t* stats) {
     return guarded([&] {
         if (!h || !stats) throw Error(ORBFE_EINVAL, "null argument");
-        if (h->last_images <= 0 || !h->last_in) throw Error(ORBFE_ESTATE, "run a batch first");
-        const Geo& g = h->geo;
-        DevBuf<int> d;
-        d.ensure(4);
-        HIPCK(hipMemset(d.p, 0, 4 * sizeof(int)));
-        if (g.ncells > 0)
-            HIPCK(launch_detect(g, h->d_cells.p, h->last_in, h->last_pitch, h->d_ws.p, h->d_cell_count.p, h->d_slots.p,
-                                h->last_images, h->last_stream, 0, d.p));
-        HIPCK(hipStreamSynchronize(h->last_stream));
-        int v[4];
-        HIPCK(hipMemcpy(v, d.p, sizeof(v), hipMemcpyDeviceToHost));
+        int v[kDetectStats];
+        detect_counters(h, 0, v);
         for (int k = 0; k < 3; ++k) stats[k] = v[k];
+    });
+}
+
+int orbfe_debug_detect_lanes(orbfe_handle h, int64_t* stats, int32_t n) {
+    return guarded([&] {
+        if (!h || !stats) throw Error(ORBFE_EINVAL, "null argument");
+        if (n < 1 || n > kDetectStats) throw Error(ORBFE_EINVAL, "n must be 1 .. 7");
+        // both launch shapes, whichever the batch took: a cell's counts do not depend on its wave's other cells
+        int v4[kDetectStats], v1[kDetectStats];
+        detect_counters(h, 4, v4);
+        detect_counters(h, 1, v1);
+        for (int k = 0; k < kDetectStats; ++k)
+            if (v4[k] != v1[k]) throw Error(ORBFE_ESTATE, "k_detect's counters differ between its two launch shapes");
+        for (int k = 0; k < n; ++k) stats[k] = v4[k];
     });
 }
 

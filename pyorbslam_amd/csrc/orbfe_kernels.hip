@@ -753,6 +753,11 @@ __device__ __forceinline__ int fd_minus_bit(int o, uint64_t m) {
 constexpr int kFdCells = 4;
 constexpr int kFdSmallCells = 1;  // cells per wave for small batches
 
+template <bool B>
+struct fd_flag {  // a compile-time switch passed to a generic lambda
+    static constexpr bool value = B;
+};
+
 __device__ __forceinline__ int lanes_below(uint64_t b) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
 }
@@ -765,7 +770,7 @@ __host__ __device__ inline int detect_roi_elems(const Geo& g, int rp) {
 }
 
 // RP: ROI pitch in u16 (48, 64 or 96; >= widest ROI + 3).  NS: staged row slots (4 rows each, >= max_rh / 4).
-// CPW: cells per wave.  ST: the debug counters of orbfe_debug_detect_stats.
+// CPW: cells per wave.  ST: the debug counters of orbfe_debug_detect_stats / orbfe_debug_detect_lanes.
 // 5 waves per SIMD (<= 96 VGPRs; 4 for the wider / taller ROI shapes, which need the registers) and
 // <= 8 KiB of LDS for KITTI / EuRoC cells: detect is bound by how many
 // cells are in flight per CU (16 -> 10 resident waves costs +32 %, measured by padding the launch's LDS).
@@ -872,7 +877,7 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
         // needs M of the A pairs only.  Should the two queues meet (a cell where more than half of the pairs
         // pass at minTh), the cell takes the one-pass path below instead (both thresholds over B).
         const bool two = g.min_th < g.ini_th;
-        const int tA = g.ini_th;
+        const int tA = two ? g.ini_th : 0x7fff;  // above every bound
         const int cap = g.fd_pq;
         int npq = 0, npa = 0;
         {
@@ -921,12 +926,16 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
                 if (ca) pq[o] = e;
                 if (cb) pq[fd_plus_bit(o, b0)] = (uint16_t)(e + 2);
                 npq += __popcll(b0) + __popcll(b1);
-                if (two) {
-                    const bool aa = __builtin_amdgcn_inverse_ballot_w64(a0), ab = __builtin_amdgcn_inverse_ballot_w64(a1);
+                // a half without an A pair (more than half of them) leaves npa and the collide rule as they are:
+                // the A emission (two inverse ballots, an mbcnt chain, two address chains and stores) runs under
+                // one scalar test
+                {   // one threshold: tA is out of reach, the A masks are empty
                     const int na = __popcll(a0) + __popcll(a1);
+                    if (ST && lane == 0 && two && na == 0) atomicAdd(&stats[6], 1);
                     // both counts only grow: once the queues would meet they stay met (collide below), and A
                     // stops writing so that B stays intact for the one-pass path
-                    if (npq + npa + na <= cap) {
+                    if (na != 0 && npq + npa + na <= cap) {
+                        const bool aa = __builtin_amdgcn_inverse_ballot_w64(a0), ab = __builtin_amdgcn_inverse_ballot_w64(a1);
                         const int oa = cap - 1 - below2(a0, a1, npa);
                         if (aa) pq[oa] = e;
                         if (ab) pq[fd_minus_bit(oa, a0)] = (uint16_t)(e + 2);
@@ -969,27 +978,44 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
         __syncthreads();
         // ---- 3. exact M of a queue's pairs -> M map; the pairs with a pixel above tl are compacted in place
         //         (entry i at qb[dir * i]: dir -1 for A at the back of pq) into the NMS queue; returns its length
-        auto m_stage = [&](uint16_t* qb, int dir, int n, int tl) {
-            int nn = 0;
+        //         The stage takes the entries [first, n) and appends to the nn entries the queue already holds
+        //         (nn <= first).  With a carry (the A queue only), the kb lanes that the last step leaves idle take
+        //         the B entries pq[0 .. kb): they store their M too and compact the pairs with a pixel above
+        //         max(minTh, 1) in place into pq[0 .. nnb), outside the stage's own compaction (a pair of both
+        //         queues would otherwise enter A's NMS queue twice); kb <= those idle lanes, so only the last step
+        //         carries.
+        auto m_stage = [&](auto carry, uint16_t* qb, int dir, int first, int n, int nn, int tl, int kb, int& nnb) {
+            constexpr bool CY = decltype(carry)::value;
+            const int ne = CY ? n + kb : n;  // entries that have a lane
+            auto slot = [&](int i) { return CY && i >= n ? pq + (i - n) : qb + dir * i; };
             // the queue entry of the next step is read one step ahead (its LDS round trip overlaps this step)
-            uint32_t e_next = lane < n ? qb[dir * lane] : 2u;  // idle lanes: pixel (0, 0)
-            for (int k0 = 0; k0 < n; k0 += 64) {
-                // every lane computes (a lane past n repeats an earlier entry of its own, harmlessly); the map
+            uint32_t e_next = first + lane < ne ? *slot(first + lane) : 2u;  // idle lanes: pixel (0, 0)
+            for (int k0 = first; k0 < n; k0 += 64) {
+                // every lane computes (a lane past ne repeats an earlier entry of its own, harmlessly); the map
                 // store and the compaction take the lanes of this step's entries (lane masks, as the pre-test)
                 const uint32_t e = e_next;
-                if (k0 + 64 + lane < n) e_next = qb[dir * (k0 + 64 + lane)];
+                if (k0 + 64 + lane < ne) e_next = *slot(k0 + 64 + lane);
                 const uint64_t inr = __builtin_amdgcn_sicmp(k0 + lane, n, 40);  // ICMP_SLT
+                const uint64_t ine = CY ? (uint64_t)__builtin_amdgcn_sicmp(k0 + lane, ne, 40) : inr;
                 const uint32_t m = fast_m_pair<S>((const uint32_t*)(roi + e) + 3 * S + 1);
                 // the u8 map keeps M itself (low byte of each biased half); odd width: the last pair's second
                 // pixel lies outside the window, its map entry is cleared after this stage
-                if (__builtin_amdgcn_inverse_ballot_w64(inr))
+                if (__builtin_amdgcn_inverse_ballot_w64(ine))
                     *(uint16_t*)(mm + e + MP) = (uint16_t)__builtin_amdgcn_perm(0u, m, 0x0c0c0200u);
                 // slots below k0 + 64 are written; every read of the queue (this step's entries, the next
                 // step's prefetch) was issued before
-                const uint64_t bh = inr & ((uint64_t)__builtin_amdgcn_sicmp((int)(m & 0x3FFu), tl, 38) |
-                                           (uint64_t)__builtin_amdgcn_sicmp((int)((m >> 16) & 0x3FFu), tl, 38));
+                auto above = [&](int t) {
+                    return (uint64_t)__builtin_amdgcn_sicmp((int)(m & 0x3FFu), t, 38) |
+                           (uint64_t)__builtin_amdgcn_sicmp((int)((m >> 16) & 0x3FFu), t, 38);
+                };
+                const uint64_t bh = inr & above(tl);
                 if (__builtin_amdgcn_inverse_ballot_w64(bh)) qb[dir * (nn + lanes_below(bh))] = (uint16_t)e;
                 nn += __popcll(bh);
+                if (CY && (ine & ~inr) != 0) {  // the carried lanes: their entries pq[0 .. kb) are all read
+                    const uint64_t bc = ine & ~inr & above(max(g.min_th, 1));
+                    if (__builtin_amdgcn_inverse_ballot_w64(bc)) pq[nnb + lanes_below(bc)] = (uint16_t)e;
+                    nnb += __popcll(bc);
+                }
             }
             // odd width: column ww (right of the window) got the outside pixel's M from the last pairs; NMS
             // reads it as a neighbour (and as that pixel's own score) and needs 0 there
@@ -1045,12 +1071,26 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
         int total = 0;
         if (two && !collide) {
             int t0, t1;
-            const int nna = m_stage(pq + cap - 1, -1, npa, max(tA, 1));
+            // A's last M step has 64 ceil(npa / 64) - npa idle lanes (on average nine tenths of the step): they take
+            // the first kb entries of B.  Such an entry outside A has M <= bound <= iniTh in both pixels, so its map
+            // entry (0 until now) changes neither A's compaction nor the iniTh NMS; an entry of both queues stores
+            // the same M twice.  The fallback then starts behind the carried entries, on their nnb0 <= kb survivors
+            // (the front of pq and the A region at its back are disjoint: npq + npa <= cap).
+            const int kb = min(((npa + 63) & ~63) - npa, npq);
+            int nnb0 = 0, none = 0;
+            const int nna = m_stage(fd_flag<true>{}, pq + cap - 1, -1, 0, npa, 0, max(tA, 1), kb, nnb0);
+            if (ST && lane == 0 && kb > 0) {
+                atomicAdd(&stats[3], 1);
+                atomicAdd(&stats[4], kb);
+            }
             nms_stage(pq + cap - 1, -1, nna, max(g.ini_th, 1), 0, t0, t1);
             total = t0;
-            if (t0 == 0) {  // minTh fallback: every pair of B (the A pairs' M is recomputed, identically)
-                if (ST && lane == 0) atomicAdd(&stats[2], 1);
-                const int nnb = m_stage(pq, 1, npq, max(g.min_th, 1));
+            if (t0 == 0) {  // minTh fallback: the rest of B (the A pairs' M is recomputed, identically)
+                if (ST && lane == 0) {
+                    atomicAdd(&stats[2], 1);
+                    atomicAdd(&stats[5], (npq - kb + 63) >> 6);
+                }
+                const int nnb = m_stage(fd_flag<false>{}, pq, 1, kb, npq, nnb0, max(g.min_th, 1), 0, none);
                 nms_stage(pq, 1, nnb, max(g.min_th, 1), 0, t0, t1);
                 total = t0;
             }
@@ -1058,7 +1098,8 @@ __global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(G
             // one pass over B at tq = min(iniTh, minTh), both thresholds in the NMS: iniTh survivors go
             // straight out, minTh survivors are staged in the (dead) ROI area and copied out only if iniTh
             // kept nothing
-            const int nnq = m_stage(pq, 1, npq, max(tq, 1));
+            int none = 0;
+            const int nnq = m_stage(fd_flag<false>{}, pq, 1, 0, npq, 0, max(tq, 1), 0, none);
             const bool fb = g.min_th != g.ini_th;
             int t0, t1;
             nms_stage(pq, 1, nnq, max(g.ini_th, 1), fb ? max(g.min_th, 1) : 0, t0, t1);
