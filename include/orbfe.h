@@ -513,6 +513,57 @@ int orbfe_vocab_bow(orbfe_vocab_handle v, const uint8_t* desc32, const int64_t* 
 /* Kernel time of the last orbfe_vocab_bow (descent + assembly, ms, HIP events), for measurement. */
 int orbfe_vocab_bow_last_ms(orbfe_vocab_handle v, float* ms);
 
+/* ---- training a vocabulary on the device (DBoW2's create: HKmeansStep / initiateClustersKMpp / setNodeWeights) ----
+ *
+ * The tree is built level by level, integer only, so the result is defined bit for bit (INTEGRATION.md has the
+ * full definition; tests/vocab_train_definition.py restates it in NumPy):
+ *   - D is the concatenation of the images' descriptors in image order.  Node 0 (the root) holds every index of D;
+ *     nodes are numbered breadth-first (depth by depth, parents ascending, a parent's children in cluster order),
+ *     NOT in DBoW2's recursion order.  A node's members stay in ascending index of D.
+ *   - A node is split iff its depth < L and it has more than one member (the root iff it has any).  With n <= k
+ *     members every member is a cluster of its own.  Otherwise: integer kmeans++ seeding drawn from splitmix64 of
+ *     seed + (32 node + j + 1) * 0x9E3779B97F4A7C15, then Lloyd iterations (assignment to the centre at the
+ *     smallest Hamming distance, lowest cluster index on ties; a centre becomes its members' bitwise majority, an
+ *     exact half setting the bit as FORB.meanValue does; an emptied cluster keeps its centre) until an assignment
+ *     repeats or max_iter iterations ran.  Clusters that end without members give no child.
+ *   - A node without children is a leaf; word ids number the leaves in id order.
+ *   - Weights: every descriptor of D descends the finished tree; Ni[w] counts the images that reach word w.
+ *     TF_IDF and IDF: log(n_frames / Ni) in double on the host (0 where Ni = 0); TF and BINARY: 1.  Inner nodes 0. */
+#define ORBFE_VOCAB_TRAIN_MAX_L 10
+typedef struct orbfe_vocab_train_params {
+    int32_t k;         /* 2 .. 20                                                       */
+    int32_t L;         /* 1 .. 10                                                       */
+    int32_t weighting; /* 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY                               */
+    int32_t scoring;   /* 0 .. 5: stored in the header only                             */
+    int32_t max_iter;  /* >= 1; 1 leaves the kmeans++ seeds as centres                  */
+    int32_t reserved;  /* 0                                                             */
+    uint64_t seed;
+} orbfe_vocab_train_params;
+/* Entry d of the per-depth arrays describes the nodes of depth d that were split. */
+typedef struct orbfe_vocab_train_stats {
+    int64_t n_desc, n_nodes, n_words;
+    int64_t nodes_split[ORBFE_VOCAB_TRAIN_MAX_L];
+    int64_t iter_sum[ORBFE_VOCAB_TRAIN_MAX_L];    /* Lloyd iterations, summed over the nodes with n > k */
+    int64_t iter_max[ORBFE_VOCAB_TRAIN_MAX_L];
+    int64_t capped[ORBFE_VOCAB_TRAIN_MAX_L];      /* nodes still changing at iteration max_iter         */
+    int64_t empty_dropped[ORBFE_VOCAB_TRAIN_MAX_L]; /* seeded clusters that ended without members       */
+    int64_t short_seeded[ORBFE_VOCAB_TRAIN_MAX_L];  /* nodes whose seeding stopped below k centres (S = 0) */
+    double depth_ms[ORBFE_VOCAB_TRAIN_MAX_L];     /* stream time of the depth (HIP events), its read-backs included */
+    double weight_ms;                             /* descent of D and the per-image word marks          */
+    double kernel_ms;                             /* the sum of the above                               */
+} orbfe_vocab_train_stats;
+/* Image f < n_frames is descriptors start[f] .. start[f] + count[f] of desc32 (32 bytes each; start and count are
+ * host arrays, so strided layouts with gaps are expressible); desc_on_device != 0 says desc32 is device memory.
+ * Synchronous, on a stream and buffers of its own.  *out is an ordinary vocabulary handle.  stats may be NULL.
+ * ORBFE_EINVAL before any device call: a parameter out of range, n_frames < 1, a negative start or count, more
+ * than 2^31 - 1 descriptors in total, a null pointer (desc32 may be NULL only when every count is 0). */
+int orbfe_vocab_train(const uint8_t* desc32, int32_t desc_on_device, const int64_t* start, const int32_t* count,
+                      int32_t n_frames, const orbfe_vocab_train_params* params, orbfe_vocab_handle* out,
+                      orbfe_vocab_train_stats* stats);
+/* Writes the text layout orbfe_vocab_load_text reads: "k L scoring weighting", then per node after the root
+ * "parent is_leaf d0 .. d31 weight", the weight as the shortest decimal that round-trips the double.  Host only. */
+int orbfe_vocab_save_text(orbfe_vocab_handle v, const char* path);
+
 /* ---- BoW-guided matching of many frame pairs (ORBMatcher.search_by_BoW_kf_f / _kf_kf, ORBMatcher.py:21-213) ----
  *
  * k_bow_match, one launch for n_pairs pairs (frame 1, frame 2) of one set of frames.  A frame is n descriptors, n

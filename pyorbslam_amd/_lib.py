@@ -40,6 +40,24 @@ class VocabInfo(C.Structure):
                 ("n_nodes", C.c_int64), ("n_words", C.c_int64), ("depth", C.c_int32), ("max_children", C.c_int32)]
 
 
+class VocabTrainParams(C.Structure):
+    """orbfe_vocab_train_params."""
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("weighting", C.c_int32), ("scoring", C.c_int32),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+ORBFE_VOCAB_TRAIN_MAX_L = 10
+VOCAB_TRAIN_DEPTH_COUNTERS = ("nodes_split", "iter_sum", "iter_max", "capped", "empty_dropped", "short_seeded")
+
+
+class VocabTrainStats(C.Structure):
+    """orbfe_vocab_train_stats: entry d of a per-depth array describes the nodes of depth d that were split."""
+    _fields_ = ([("n_desc", C.c_int64), ("n_nodes", C.c_int64), ("n_words", C.c_int64)] +
+                [(k, C.c_int64 * ORBFE_VOCAB_TRAIN_MAX_L) for k in VOCAB_TRAIN_DEPTH_COUNTERS] +
+                [("depth_ms", C.c_double * ORBFE_VOCAB_TRAIN_MAX_L), ("weight_ms", C.c_double),
+                 ("kernel_ms", C.c_double)])
+
+
 ORBFE_ABI_VERSION = 9
 ORBFE_BOW_MAX_FRAME = 8192  # the longest frame k_bow_assemble takes (include/orbfe.h)
 # flags of BowOut.status
@@ -186,6 +204,9 @@ SIGNATURES = {
     "orbfe_vocab_bow_scratch_bytes": [C.c_int32, C.c_int64, C.POINTER(C.c_int64)],
     "orbfe_vocab_bow": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BowOut)],
     "orbfe_vocab_bow_last_ms": [C.c_void_p, C.POINTER(C.c_float)],
+    "orbfe_vocab_train": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VocabTrainParams),
+                          C.POINTER(C.c_void_p), C.POINTER(VocabTrainStats)],
+    "orbfe_vocab_save_text": [C.c_void_p, C.c_char_p],
     "orbfe_kfdb_create": [C.c_int64, C.c_int64, C.POINTER(C.c_void_p)],
     "orbfe_kfdb_destroy": [C.c_void_p],
     "orbfe_kfdb_add": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],

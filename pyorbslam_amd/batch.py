@@ -129,6 +129,31 @@ class StereoFrontEnd:
                  b["scratch"].numel() * 8, C.c_void_p(stream_ptr))
         return n_frames
 
+    def train_vocabulary(self, k: int = 10, L: int = 5, weighting: str = "TF_IDF", scoring: str = "L1_NORM",
+                         side: str = "left", seed: int = 0, max_iter: int = 64):
+        """Train a vocabulary on the last batch's resident descriptors (orbfe_vocab_train with desc_on_device = 1 on
+        the view bow() uses): image f is the first count[f] descriptors of its kp_cap slots.  side as in bow().  The
+        counts are fetched to the host first, which synchronises the device.  Returns a TemplatedVocabulary ready
+        for bow()."""
+        from .vocabulary import TemplatedVocabulary
+        if side not in ("left", "both"):
+            raise ValueError('side must be "left" or "both"')
+        v = BatchView()
+        call("orbfe_batch_view_get", self._h, C.byref(v))
+        step = 2 if side == "left" else 1
+        n_frames = v.n_images // step
+        if n_frames < 1:
+            raise ValueError("no batch has been enqueued")
+        count = np.zeros(v.n_images, np.int32)
+        hip = _lib.lib()  # the HIP runtime the library is linked against
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        if hip.hipDeviceSynchronize() != 0 or hip.hipMemcpy(ptr(count), C.c_void_p(v.count), count.nbytes, 2) != 0:
+            raise RuntimeError("reading the batch's counts from the device failed")  # 2: hipMemcpyDeviceToHost
+        count = np.clip(count[::step], 0, self.kp_cap).astype(np.int32)
+        start = np.arange(n_frames, dtype=np.int64) * (step * self.kp_cap)
+        voc = TemplatedVocabulary(k, L, weighting, scoring)
+        return voc.train_arrays(v.desc, True, start, count, seed, max_iter)
+
     def fetch_bow(self, i: int):
         """vocabulary.BowArrays of frame i of the last bow(); synchronises the device."""
         import torch

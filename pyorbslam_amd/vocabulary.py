@@ -24,7 +24,20 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
-from ._lib import ORBFE_BOW_MAX_FRAME, ORBFE_EFORMAT, ORBFE_EREJECT, BowOut, VocabInfo, call, check, lib, ptr
+from ._lib import (ORBFE_BOW_MAX_FRAME, ORBFE_EFORMAT, ORBFE_EREJECT, VOCAB_TRAIN_DEPTH_COUNTERS, BowOut, VocabInfo,
+                   VocabTrainParams, VocabTrainStats, call, check, lib, ptr)
+
+# the header codes of DBoW2's WeightingType and ScoringType
+WEIGHTING_CODES = {"TF_IDF": 0, "TF": 1, "IDF": 2, "BINARY": 3}
+SCORING_CODES = {"L1_NORM": 0, "L2_NORM": 1, "CHI_SQUARE": 2, "KL": 3, "BHATTACHARYYA": 4, "DOT_PRODUCT": 5}
+
+
+def _code(table, value, what):
+    if isinstance(value, str):
+        if value not in table:
+            raise ValueError(f"unknown {what} {value!r}: one of {sorted(table)}")
+        return table[value]
+    return int(value)  # the header integer load_from_text_file leaves in place of the string
 
 
 # ScoringObject.py:30-92, restated for the host (no device path)
@@ -160,8 +173,50 @@ class TemplatedVocabulary:
         self._replace(h)
         return self
 
+    def create(self, training_features, seed=0, max_iter=64):
+        """DBoW2's create: train the tree on the device (orbfe_vocab_train) from one (n_i, 32) uint8 array per image.
+        k, L, weighting and scoring are the constructor's.  Returns self."""
+        frames = [np.ascontiguousarray(f, np.uint8).reshape(-1, 32) for f in training_features]
+        count = np.array([len(f) for f in frames], np.int32)
+        start = np.zeros(len(frames), np.int64)
+        np.cumsum(count[:-1], out=start[1:])
+        d = np.ascontiguousarray(np.concatenate(frames)) if frames else np.zeros((0, 32), np.uint8)
+        return self.train_arrays(d.ctypes.data if len(d) else None, False, start, count, seed, max_iter)
+
+    def train_arrays(self, desc_ptr, on_device, start, count, seed=0, max_iter=64):
+        """orbfe_vocab_train over image f = descriptors start[f] .. start[f] + count[f] of the host or device memory
+        at desc_ptr, which the caller keeps alive during the call.  Returns self."""
+        prm = VocabTrainParams(int(self.k), int(self.L), _code(WEIGHTING_CODES, self.weighting, "weighting"),
+                               _code(SCORING_CODES, self.scoring, "scoring"), int(max_iter), 0,
+                               int(seed) & 0xFFFFFFFFFFFFFFFF)
+        start = np.ascontiguousarray(start, np.int64)
+        count = np.ascontiguousarray(count, np.int32)
+        h, st = C.c_void_p(), VocabTrainStats()
+        call("orbfe_vocab_train", C.c_void_p(desc_ptr), 1 if on_device else 0, ptr(start), ptr(count), len(count),
+             C.byref(prm), C.byref(h), C.byref(st))
+        self._replace(h)
+        self._train_stats = st
+        return self
+
+    def train_stats(self) -> dict:
+        """Counters and times of the create() that built this vocabulary (orbfe_vocab_train_stats); the per-depth
+        lists have one entry per depth 0 .. 9 of the nodes that were split."""
+        st = getattr(self, "_train_stats", None)
+        if st is None:
+            raise RuntimeError("this vocabulary was not trained by create()")
+        out = dict(n_desc=int(st.n_desc), n_nodes=int(st.n_nodes), n_words=int(st.n_words),
+                   weight_ms=float(st.weight_ms), kernel_ms=float(st.kernel_ms), depth_ms=list(st.depth_ms))
+        for key in VOCAB_TRAIN_DEPTH_COUNTERS:
+            out[key] = list(getattr(st, key))
+        return out
+
+    def save_to_text_file(self, filename) -> None:
+        """The text layout load_from_text_file (here and in the reference) reads (orbfe_vocab_save_text)."""
+        call("orbfe_vocab_save_text", self._handle(), str(filename).encode())
+
     def _replace(self, h):
         old, self._h = self._h, h
+        self._train_stats = None  # train_arrays sets them after installing its tree
         if old is not None:
             lib().orbfe_vocab_destroy(old)
 
