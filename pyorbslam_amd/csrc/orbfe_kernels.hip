@@ -277,24 +277,31 @@ typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 
 // Horizontal taps of a group's 4th pixel from a window of its own (LevelGeo::wide): A3 = LDS byte address of
 // its source pixel sx3, aa = its (a0, a1) weights.
-__device__ __forceinline__ uint32_t resize_tap3(uint32_t A3, uint32_t aa) {
+// (W3 = A3 - o the window's aligned address, o = A3 & 3: k_resize_rows hoists them out of its row loop)
+__device__ __forceinline__ uint32_t resize_tap3_al(uint32_t W3, uint32_t o, uint32_t aa) {
     typedef __attribute__((address_space(3))) const uint32_t lds_c32;
-    const uint32_t o = A3 & 3u;
-    lds_c32* w = (lds_c32*)(uintptr_t)(A3 - o);
+    lds_c32* w = (lds_c32*)(uintptr_t)W3;
     const uint32_t x = __builtin_amdgcn_alignbyte(w[1], w[0], o);
     return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(x, x, 0x0c010c00u)),
                                   __builtin_bit_cast(us2, aa), 0u, false);
 }
-constexpr int kRsSlots = 16;  // staged dwords per thread per pass
+__device__ __forceinline__ uint32_t resize_tap3(uint32_t A3, uint32_t aa) {
+    const uint32_t o = A3 & 3u;
+    return resize_tap3_al(A3 - o, o, aa);
+}
+constexpr int kRsSlots = 16;     // k_resize_cascade: staged dwords per thread per pass (it takes half)
+constexpr int kRsRowSlots = 24;  // k_resize_rows: staged dwords per thread per pass (a short pass takes 8 or 16)
 
 // k_resize_rows: one workgroup per band of LevelGeo::rs_rows output rows, the compute mapped so that a wave's
 // row is uniform.  The block holds R_s row sets of W_g waves (64 W_g >= the level's groups): lane
 // (w % W_g) * 64 + lane of a set owns one 4-pixel group for the whole band, its x selectors / weights in
-// registers; set w / W_g takes rows set, set + R_s, ...  A row's source-row LDS addresses and vertical
-// weights come from scalar loads of the y table, the store is a buffer store with the row offset in soffset:
-// per 4 pixels only the taps, the vertical rounding and the pack are VALU work.  Blocks of
-// 256 <= 64 W_g R_s <= 512 threads (the host picks R_s).
-template <bool MULTI>
+// registers; set w / W_g takes a run of consecutive rows of the band.  A row's source-row LDS addresses and
+// vertical weights come from scalar loads of the y table, the store is a buffer store with the row offset in
+// soffset: per 4 pixels only the taps, the vertical rounding and the pack are VALU work.  Blocks of
+// NT = 64 (W_g R_s + remainder wave) threads, 256 <= NT <= 512 (the host picks R_s).  AL4: the source row
+// stride is a multiple of 4 (every derived level's pitch, the input when its width is), so a group's window
+// has the same misalignment in every source row.
+template <bool MULTI, bool AL4, int NT>
 __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t* __restrict__ in, int64_t in_pitch,
                                                      uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
                                                      const ResizeY* __restrict__ yt, int wg, int remw, int wgl,
@@ -309,7 +316,7 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
     const LevelGeo& P = g.lv[l - 1];
     int bx, img;
     xcd_block(bx, img);
-    const int t = threadIdx.x, nthr = blockDim.x;
+    const int t = threadIdx.x;
     if (zero_word && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) *zero_word = 0;
     const int rows = L.rs_rows;  // kRsRows, fewer for very wide levels (LevelGeo::rs_rows)
     const int dy0 = bx * rows, nrow = min(rows, L.h - dy0);
@@ -329,7 +336,7 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
     // rows of the band: lane j owns group wg * 64 + j % rem and rows j / rem, + 64 / rem, ... (a per-lane
     // row), instead of a mostly idle row-uniform wave per row.  A set has wgl <= 8 waves: when a level has
     // more chunks than that (rows wider than 2 048 px), a set's wave walks chunks c, c + wgl, ...
-    const int wv = t >> 6, fullw = (nthr >> 6) - remw, nset = fullw / wgl;
+    const int wv = t >> 6, fullw = NT / 64 - remw, nset = fullw / wgl;
     const bool remwave = wv >= fullw;
     const int set = __builtin_amdgcn_readfirstlane(remwave ? 0 : wv / wgl);
     const int rem = ngrp - wg * 64, lane = t & 63;
@@ -356,28 +363,39 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
         }
     };
     chunk(ch);
-    // staging by the first 256 threads (blocks have >= 256): compile-time strides, immediate LDS offsets.  The
-    // loads go through a wave-uniform buffer resource: one VGPR offset for all slots, the slot and pass in the
-    // SGPR offset, no 64-bit address arithmetic; the range test is one compare of the thread index against a
-    // wave-uniform limit per slot, shared by the load and the LDS store (≈ 8 VALU per staged dword before, a
-    // quarter of the stage's VALU).  The test must guard the load itself: the resource's bounds check does not
-    // include the SGPR offset, so an unguarded slot past the run reads past the buffer.
-    if (t < 256) {
+    // staging by every thread of the block: compile-time strides (NT), immediate LDS offsets, and every load of
+    // a pass (up to kRsRowSlots dwords per thread; KITTI's bands take one pass, level 1 its 21 slots) issued
+    // before the first wait.  The loads go through a wave-uniform buffer resource: one VGPR offset for all
+    // slots, the slot and pass in the SGPR offset, no 64-bit address arithmetic; the range test is one compare
+    // of the thread index against a wave-uniform limit per slot, shared by the load and the LDS store.  The
+    // test must guard the load itself: the resource's bounds check does not include the SGPR offset, so an
+    // unguarded slot past the run reads past the buffer.
+    {
         const __amdgpu_buffer_rsrc_t rsrc = bounded_rsrc((const void*)(uintptr_t)gsrc, (uint32_t)(4 * ndw));
-        for (int base = 0; base < ndw; base += 256 * kRsSlots) {
-            const int left = ndw - base;
-            uint32_t v[kRsSlots];
+        // one pass: S slots per thread, every load before the first LDS store
+        auto pass = [&](auto nslot, int base, int left) {
+            constexpr int S = decltype(nslot)::value;
+            uint32_t v[S];
 #pragma unroll
-            for (int k = 0; k < kRsSlots; ++k) {
+            for (int k = 0; k < S; ++k) {
                 v[k] = 0u;
-                if (t < left - 256 * k)
-                    v[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (uint32_t)(4 * t), (uint32_t)(4 * (base + 256 * k)), 0);
+                if (t < left - NT * k)
+                    v[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (uint32_t)(4 * t), (uint32_t)(4 * (base + NT * k)), 0);
             }
             // one LDS address per pass (immediate offsets per slot)
             lds_w32* sp = s_src + base + t;
 #pragma unroll
-            for (int k = 0; k < kRsSlots; ++k)
-                if (t < left - 256 * k) sp[256 * k] = v[k];
+            for (int k = 0; k < S; ++k)
+                if (t < left - NT * k) sp[NT * k] = v[k];
+        };
+        for (int base = 0; base < ndw; base += NT * kRsRowSlots) {
+            const int left = ndw - base;  // wave-uniform: a scalar branch picks the pass's slot count
+            if (left <= NT * kRsRowSlots / 3)
+                pass(std::integral_constant<int, kRsRowSlots / 3>{}, base, left);
+            else if (left <= NT * (kRsRowSlots * 2 / 3))
+                pass(std::integral_constant<int, kRsRowSlots * 2 / 3>{}, base, left);
+            else
+                pass(std::integral_constant<int, kRsRowSlots>{}, base, left);
         }
     }
     __syncthreads();
@@ -388,60 +406,87 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
         const int dx = 4 * grp;
         const bool tail = dx + 3 >= L.xvec;  // FixedPtCast<int, uchar, 22> past the last SIMD block
         const uint32_t lsrc = src_lds + (uint32_t)sh0 + (uint32_t)sx0;
-        // psy: the previous row's second source row.  Full waves walk consecutive rows, and a row's first
-        // source row is mostly the previous row's second: its taps are reused, not recomputed.  The two tap
-        // sets alternate between ha and hb over a 2-row unrolled loop, so the reuse needs no register copies
-        // (4-5 v_mov per row and 4-pixel group before)
-        int psy = -1;
-        auto row = [&](int rr, uint32_t (&h0)[4], uint32_t (&h1)[4], bool reuse) {
-            const ResizeY y = yb[rr];  // full waves: uniform, scalar loads
-            const uint32_t r0 = (uint32_t)((y.sy0 - ys_lo) * sstride), r1 = (uint32_t)((y.sy1 - ys_lo) * sstride);
-            const uint32_t B0 = (uint32_t)y.b0 << 12, B1 = (uint32_t)y.b1 << 12;
-            auto taps = [&](uint32_t roff, uint32_t (&h)[4]) {
-                const uint32_t A = lsrc + roff, o = A & 3u;
-                lds_u32* w = (lds_u32*)(uintptr_t)(A - o);
-                const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-                const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o);
-                h[0] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.x)),
-                                              __builtin_bit_cast(us2, aa.x), 0u, false);
-                h[1] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.y)),
-                                              __builtin_bit_cast(us2, aa.y), 0u, false);
-                h[2] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.z)),
-                                              __builtin_bit_cast(us2, aa.z), 0u, false);
-                h[3] = L.wide ? resize_tap3(A + d3, aa.w)
-                              : __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.w)),
-                                                       __builtin_bit_cast(us2, aa.w), 0u, false);
+        // AL4: the window's misalignment and aligned base, the same in every source row of the band
+        const uint32_t lo = lsrc & 3u, lal = lsrc - lo, lo3 = (lsrc + d3) & 3u, lal3 = lsrc + d3 - lo3;
+        // TAIL: a wave with a lane in the scalar tail (a level's last groups), or the remainder wave, keeps the
+        // taps unmasked for resize_tail and tests each lane per row; every other wave masks a source row's taps
+        // once, where they are produced (reused taps would be masked twice), and packs without the test
+        auto band = [&](auto tail_c) {
+            constexpr bool TAIL = decltype(tail_c)::value;
+            // psy: the previous row's second source row.  Full waves walk consecutive rows, and a row's first
+            // source row is mostly the previous row's second: its taps are reused, not recomputed.  The two tap
+            // sets alternate between ha and hb over a 2-row unrolled loop, so the reuse needs no register copies
+            // (4-5 v_mov per row and 4-pixel group before)
+            int psy = -1;
+            auto row = [&](int rr, uint32_t (&h0)[4], uint32_t (&h1)[4], bool reuse) {
+                const ResizeY y = yb[rr];  // full waves: uniform, scalar loads
+                const uint32_t r0 = (uint32_t)((y.sy0 - ys_lo) * sstride), r1 = (uint32_t)((y.sy1 - ys_lo) * sstride);
+                const uint32_t B0 = (uint32_t)y.b0 << 12, B1 = (uint32_t)y.b1 << 12;
+                auto taps = [&](uint32_t roff, uint32_t (&h)[4]) {
+                    const uint32_t A = lsrc + roff, o = AL4 ? lo : A & 3u;
+                    lds_u32* w = (lds_u32*)(uintptr_t)(AL4 ? lal + roff : A - o);
+                    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+                    const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o);
+                    h[0] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.x)),
+                                                  __builtin_bit_cast(us2, aa.x), 0u, false);
+                    h[1] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.y)),
+                                                  __builtin_bit_cast(us2, aa.y), 0u, false);
+                    h[2] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.z)),
+                                                  __builtin_bit_cast(us2, aa.z), 0u, false);
+                    h[3] = L.wide ? (AL4 ? resize_tap3_al(lal3 + roff, lo3, aa.w) : resize_tap3(A + d3, aa.w))
+                                  : __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.w)),
+                                                           __builtin_bit_cast(us2, aa.w), 0u, false);
+                    if (!TAIL) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) h[k] &= ~15u;
+                    }
+                };
+                // h0 holds the taps of source row psy (the previous row's h1) when reuse applies
+                if (!(reuse && y.sy0 == psy)) taps(r0, h0);
+                taps(r1, h1);
+                if (reuse) psy = y.sy1;
+                uint32_t out;
+                if (TAIL) {
+                    uint32_t v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = (__umulhi(h0[k] & ~15u, B0) + __umulhi(h1[k] & ~15u, B1) + 2) >> 2;
+                    if (tail) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (dx + k >= L.xvec) v[k] = resize_tail(h0[k] * (B0 >> 12) + h1[k] * (B1 >> 12), L.area);
+                    }
+                    out = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+                } else {
+                    // the sums + 2 are below 2^10: two to a dword at 16-bit spacing, one shift for both, one v_perm
+                    // for the four bytes (5 instructions for 7)
+                    uint32_t s[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s[k] = __umulhi(h0[k], B0) + __umulhi(h1[k], B1);
+                    const uint32_t p01 = ((s[1] << 16) + (s[0] + 0x20002u)) >> 2, p23 = ((s[3] << 16) + (s[2] + 0x20002u)) >> 2;
+                    out = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+                }
+                // pixels past L.w land in the row's pitch padding
+                __builtin_amdgcn_raw_buffer_store_b32(out, rd, (uint32_t)dx, (uint32_t)(rr * L.pitch), 0);
             };
-            // h0 holds the taps of source row psy (the previous row's h1) when reuse applies
-            if (!(reuse && y.sy0 == psy)) taps(r0, h0);
-            taps(r1, h1);
-            if (reuse) psy = y.sy1;
-            uint32_t v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = (__umulhi(h0[k] & ~15u, B0) + __umulhi(h1[k] & ~15u, B1) + 2) >> 2;
-            if (tail) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (dx + k >= L.xvec) v[k] = resize_tail(h0[k] * (B0 >> 12) + h1[k] * (B1 >> 12), L.area);
+            uint32_t ha[4] = {0u, 0u, 0u, 0u}, hb[4] = {0u, 0u, 0u, 0u};
+            if (!(TAIL && remwave)) {  // set s: rows [s * per, (s + 1) * per), consecutive
+                const int per = (nrow + nset - 1) / nset, rend = min(set * per + per, nrow);
+                int rr = set * per;
+                for (; rr + 1 < rend; rr += 2) {
+                    row(rr, ha, hb, true);
+                    row(rr + 1, hb, ha, true);
+                }
+                if (rr < rend) row(rr, ha, hb, true);
+            } else {
+                for (int rr = row0; rr < nrow; rr += rstep) row(rr, ha, hb, false);
             }
-            // pixels past L.w land in the row's pitch padding
-            __builtin_amdgcn_raw_buffer_store_b32(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24), rd, (uint32_t)dx,
-                                                  (uint32_t)(rr * L.pitch), 0);
         };
-        uint32_t ha[4] = {0u, 0u, 0u, 0u}, hb[4] = {0u, 0u, 0u, 0u};
-        if (!remwave) {  // set s: rows [s * per, (s + 1) * per), consecutive
-            const int per = (nrow + nset - 1) / nset, rend = min(set * per + per, nrow);
-            psy = -1;
-            int rr = set * per;
-            for (; rr + 1 < rend; rr += 2) {
-                row(rr, ha, hb, true);
-                row(rr + 1, hb, ha, true);
-            }
-            if (rr < rend) row(rr, ha, hb, true);
-        } else {
-            for (int rr = row0; rr < nrow; rr += rstep) row(rr, ha, hb, false);
-        }
-        if (!MULTI) return;  // one chunk per wave (every level up to 2 048 px): round 3's code exactly
+        // wave-uniform (the ballot is over the lanes still here: the chunk's owners)
+        if (__builtin_amdgcn_ballot_w64(tail || remwave) != 0)
+            band(std::true_type{});
+        else
+            band(std::false_type{});
+        if (!MULTI) return;  // one chunk per wave (every level up to 2 048 px)
         ch += ch_step;
         if (ch >= ch_end) return;
         chunk(ch);
@@ -3992,6 +4037,17 @@ __global__ __launch_bounds__(256) void k_hamming_search(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------- launchers
+template <bool AL4>
+static auto resize_rows_kernel(int threads) {
+    switch (threads) {
+        case 256: return k_resize_rows<false, AL4, 256>;
+        case 320: return k_resize_rows<false, AL4, 320>;
+        case 384: return k_resize_rows<false, AL4, 384>;
+        case 448: return k_resize_rows<false, AL4, 448>;
+        default: return k_resize_rows<false, AL4, 512>;
+    }
+}
+
 hipError_t launch_resize(const Geo& g, int l, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
                          const ResizeY* yt, int n_images, hipStream_t s, bool remainder_wave, int* zero_word) {
     const LevelGeo& L = g.lv[l];  // LDS sized for this level (its bands' source rows)
@@ -4006,12 +4062,15 @@ hipError_t launch_resize(const Geo& g, int l, const uint8_t* in, int64_t in_pitc
     const int remw = (remainder_wave && ngrp >= 64 && wg0 <= 8 && rem > 0 && rem < 40) ? 1 : 0;
     const int wg = remw ? ngrp / 64 : wg0;
     const int wgl = std::min(wg, 8 - remw);
-    const int sets = std::max(1, (4 - remw + wgl - 1) / wgl);  // >= 256 threads per block (the staging threads)
+    const int sets = std::max(1, (4 - remw + wgl - 1) / wgl);  // >= 256 threads per block
     const int threads = 64 * (wgl * sets + remw);
     if (threads < 256 || threads > 512) return hipErrorInvalidConfiguration;
-    // MULTI: a wave walks several 64-group chunks (levels wider than 2 048 px); the one-chunk form is
-    // instantiated apart (the loop around it cost 3 % on KITTI, tools/dbg/mb_ab.sh, round 4)
-    auto k = wg > wgl ? k_resize_rows<true> : k_resize_rows<false>;
+    // MULTI: a wave walks several 64-group chunks (levels wider than 2 048 px; always 8 waves, one set); the
+    // one-chunk form is instantiated apart (the loop around it cost 3 % on KITTI, tools/dbg/mb_ab.sh, round 4),
+    // per block size (the staging's strides) and per alignment of the source row stride
+    const bool al4 = (l >= 2 ? g.lv[l - 1].pitch : g.W) % 4 == 0;
+    const auto k = wg > wgl ? (al4 ? k_resize_rows<true, true, 512> : k_resize_rows<true, false, 512>)
+                            : (al4 ? resize_rows_kernel<true>(threads) : resize_rows_kernel<false>(threads));
     hipLaunchKernelGGL(k, grid, dim3(threads), (size_t)L.rs_nsrc * L.rs_sp + 16, s, g, l, in, in_pitch, ws, xt, yt, wg,
                        remw, wgl, zero_word);
     return hipGetLastError();
