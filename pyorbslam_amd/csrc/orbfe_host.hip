@@ -2147,7 +2147,9 @@ static void detect_counters(orbfe_ctx* h, int cells_per_wave, int* v) {
     const Geo& g = h->geo;
     DevBuf<int> d;
     d.ensure(kDetectStats);
-    HIPCK(hipMemset(d.p, 0, kDetectStats * sizeof(int)));
+    // on the kernel's own stream: it is non-blocking, so a memset on the null stream is not ordered before the launch
+    // and could clear counters the kernel has already added to
+    HIPCK(hipMemsetAsync(d.p, 0, kDetectStats * sizeof(int), h->last_stream));
     if (g.ncells > 0)
         HIPCK(launch_detect(g, h->d_cells.p, h->last_in, h->last_pitch, h->d_ws.p, h->d_cell_count.p, h->d_slots.p,
                             h->last_images, h->last_stream, cells_per_wave, d.p));
@@ -2193,7 +2195,7 @@ int orbfe_debug_cascade_profile(orbfe_handle h, int64_t* marks, int64_t n_marks,
         if (n_marks < need) throw Error(ORBFE_ECAPACITY, "buffer too small (32 marks per image and strip)");
         DevBuf<long long> d;
         d.ensure(need);
-        HIPCK(hipMemset(d.p, 0, need * sizeof(long long)));
+        HIPCK(hipMemsetAsync(d.p, 0, need * sizeof(long long), h->last_stream));  // ordered before the launch
         HIPCK(launch_resize_cascade(g, h->last_in, h->last_pitch, h->d_ws.p, h->d_xt.p, h->d_yt.p, cs->tab.p, cs->S,
                                     cs->off_b, cs->off_x, cs->lds, n, h->last_stream, nullptr, d.p));
         HIPCK(hipStreamSynchronize(h->last_stream));
@@ -2210,7 +2212,7 @@ int orbfe_debug_octree_profile(orbfe_handle h, int64_t* marks, int64_t n) {
         if (n < need) throw Error(ORBFE_ECAPACITY, "buffer too small");
         DevBuf<long long> d;
         d.ensure(need);
-        HIPCK(hipMemset(d.p, 0, need * sizeof(long long)));
+        HIPCK(hipMemsetAsync(d.p, 0, need * sizeof(long long), h->last_stream));  // ordered before the launch
         HIPCK(launch_octree(g, h->d_cells.p, h->d_cell_count.p, h->d_slots.p, h->d_octab.p, h->d_kd.p, h->d_kn.p,
                             h->d_lvl_kp.p, h->d_lvl_count.p, h->d_overflow.p, h->maxcell, h->last_images, h->last_stream,
                             0, d.p));

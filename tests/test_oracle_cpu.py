@@ -114,6 +114,27 @@ def test_fast_oracle_vs_definition(seed):
     assert got == _fast_brute(img, th)
 
 
+@pytest.mark.parametrize("th", [0, 1, 254, 255])
+def test_fast_oracle_vs_definition_at_the_threshold_ends(th):
+    """Thresholds 0, 1, 254 and 255 on black and white images with dots of 0 / 1 / 2 / 254 / 255 (M = 1, 2, 254 and
+    255, bright and dark), isolated and as neighbours: a score of 0 is never a strict maximum, M = 255 passes 254."""
+    for bg, dots in ((0, (255, 254, 1, 2)), (255, (0, 1, 254, 253)), (1, (0, 255, 2, 3))):
+        img = np.full((24, 40), bg, np.uint8)
+        for i, v in enumerate(dots):
+            img[6, 5 + 8 * i] = v                 # isolated
+            img[15, 5 + 8 * i] = v                # beside the next dot of the list
+            img[16, 6 + 8 * i] = dots[(i + 1) % 4]
+        got = [tuple(r) for r in O.fast(img, th).tolist()]
+        exp = _fast_brute(img, th)
+        assert got == exp, (th, bg)
+        if th == 0 and bg == 0:
+            assert (5, 6, 254) in got and (21, 6, 0) not in got and (29, 6, 1) in got
+        if th == 255:
+            assert got == []
+        if th == 254 and bg in (0, 255):
+            assert {r for _, _, r in got} == {254}
+
+
 # ----------------------------------------------------------------------------------- resize / blur
 def _resize_py(src, dw, dh, simd):
     """cv::resize INTER_LINEAR 8U restated with numpy (coefficients in float32 / float64 like OpenCV)."""
