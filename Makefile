@@ -4,12 +4,14 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-math -Wall \
             -munsafe-fp-atomics -Wno-unused-result
-SRC := pyorbslam_amd/csrc/orbfe_kernels.hip pyorbslam_amd/csrc/orbfe_host.hip pyorbslam_amd/csrc/orbfe_vocab.hip \
+SRC := pyorbslam_amd/csrc/orbfe_kernels.hip pyorbslam_amd/csrc/orbfe_resize.hip pyorbslam_amd/csrc/orbfe_detect.hip \
+       pyorbslam_amd/csrc/orbfe_host.hip pyorbslam_amd/csrc/orbfe_vocab.hip \
        pyorbslam_amd/csrc/orbfe_kfdb.hip pyorbslam_amd/csrc/orbfe_bowmatch.hip \
        pyorbslam_amd/csrc/orbfe_trimatch.hip pyorbslam_amd/csrc/orbfe_fuse.hip \
        pyorbslam_amd/csrc/orbfe_vocabtrain.hip
 CSRC := pyorbslam_amd/csrc/orbfe_png.cpp
 HDR := pyorbslam_amd/csrc/orbfe_common.h pyorbslam_amd/csrc/orbfe_kernels.h pyorbslam_amd/csrc/orbfe_host_util.h include/orbfe.h \
+       pyorbslam_amd/csrc/orbfe_device.h pyorbslam_amd/csrc/orbfe_internal.h \
        pyorbslam_amd/csrc/brief_pattern.inc pyorbslam_amd/csrc/brief_distinct.inc \
        pyorbslam_amd/csrc/brief_slot_order.inc
 LIB := pyorbslam_amd/_lib/liborbfe.so

@@ -29,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "orbfe_device.h"
 #include "orbfe_host_util.h"
 
 using namespace orbfe;
@@ -120,16 +121,6 @@ __device__ __forceinline__ void bm_run(const BmSide& s, int r, int& a, int& b) {
     b = s.end[r];
     a = a < 0 ? 0 : (a > s.cap ? s.cap : a);
     b = b < a ? a : (b > s.cap ? s.cap : b);
-}
-
-__device__ __forceinline__ unsigned bm_dist(const uint4& a, const uint4& b, const uint4& qa, const uint4& qb) {
-    return __popc(a.x ^ qa.x) + __popc(a.y ^ qa.y) + __popc(a.z ^ qa.z) + __popc(a.w ^ qa.w) + __popc(b.x ^ qb.x) +
-           __popc(b.y ^ qb.y) + __popc(b.z ^ qb.z) + __popc(b.w ^ qb.w);
-}
-
-// lane j's value of v, j wave-uniform
-__device__ __forceinline__ unsigned bm_lane(unsigned v, int j) {
-    return (unsigned)__builtin_amdgcn_readlane((int)v, j);
 }
 
 // the two smallest of the wave's 64 distinct keys (m1 in, m2 = all ones in), in every lane
@@ -230,17 +221,17 @@ __global__ __launch_bounds__(64 * kBmWaves) void k_bow_match(BmFrames fr, const 
             }
             const int i1 = __builtin_amdgcn_readlane(my_i1, j);
             if (i1 < 0) continue;
-            const uint4 qa = make_uint4(bm_lane(ma.x, j), bm_lane(ma.y, j), bm_lane(ma.z, j), bm_lane(ma.w, j));
-            const uint4 qb = make_uint4(bm_lane(mb.x, j), bm_lane(mb.y, j), bm_lane(mb.z, j), bm_lane(mb.w, j));
+            const uint4 qa = make_uint4(lane_value(ma.x, j), lane_value(ma.y, j), lane_value(ma.z, j), lane_value(ma.w, j));
+            const uint4 qb = make_uint4(lane_value(mb.x, j), lane_value(mb.y, j), lane_value(mb.z, j), lane_value(mb.w, j));
             int best1 = 256, best2 = 256, bestpos = -1;
             for (int c = 0; c < len2; c += 64) {
                 const int pos = c + lane;
                 unsigned d = 256;
                 if (c == 0) {
-                    if (i2_0 >= 0 && !blk[i2_0]) d = bm_dist(ea, eb, qa, qb);
+                    if (i2_0 >= 0 && !blk[i2_0]) d = hamming256(ea, eb, qa, qb);
                 } else if (pos < len2) {
                     const int i2 = s2.idx[a2 + pos];
-                    if ((unsigned)i2 < (unsigned)n2 && !blk[i2]) d = bm_dist(s2.desc[2 * i2], s2.desc[2 * i2 + 1], qa, qb);
+                    if ((unsigned)i2 < (unsigned)n2 && !blk[i2]) d = hamming256(s2.desc[2 * i2], s2.desc[2 * i2 + 1], qa, qb);
                 }
                 unsigned m1 = (d << 16) | (unsigned)pos, m2 = 0xFFFFFFFFu;
                 bm_min2(m1, m2);
@@ -314,16 +305,12 @@ struct Matcher {
     DevBuf<int8_t> d_bin;
     std::vector<int32_t> h_match;  // host staging of match12, match21
     std::vector<int8_t> h_bin;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_ms = 0.f;
+    TimedStream t;
 };
 Matcher& matcher() {
     static Matcher* m = new Matcher;
     return *m;
 }
-
-std::string at_frame(int32_t f, const char* what) { return "frame " + std::to_string(f) + ": " + what; }
 
 }  // namespace
 
@@ -391,43 +378,22 @@ int orbfe_bow_match(const uint8_t* desc32, const float* angle, const uint8_t* el
                                               std::to_string(ORBFE_BOW_MAX_FRAME) + " per frame");
             if (n > 0 && (!desc32 || !angle)) throw Error(ORBFE_EINVAL, "null argument");
             if (nn > 0 && (!fv_node || !fv_end)) throw Error(ORBFE_EINVAL, "null argument");
-            seen.assign((size_t)n, 0);
-            int64_t prev_end = 0;
-            for (int64_t r = 0; r < nn; ++r) {
-                const int64_t at = fv_off[f] + r;
-                if (r > 0 && fv_node[at] <= fv_node[at - 1])
-                    throw Error(ORBFE_EINVAL, at_frame(f, "feature vector nodes must be strictly ascending"));
-                const int64_t end = fv_end[at];
-                if (end < prev_end) throw Error(ORBFE_EINVAL, at_frame(f, "feature vector run ends must not decrease"));
-                if (end > n) throw Error(ORBFE_EINVAL, at_frame(f, "a feature vector run ends past the index count"));
-                if (end > prev_end && !fv_idx) throw Error(ORBFE_EINVAL, "null argument");
-                for (int64_t k = prev_end; k < end; ++k) {
-                    const int32_t i = fv_idx[off[f] + k];
-                    if (i < 0 || i >= n) throw Error(ORBFE_EINVAL, at_frame(f, "a feature index is out of range"));
-                    if (seen[i]) throw Error(ORBFE_EINVAL, at_frame(f, "a feature index appears twice"));
-                    seen[i] = 1;
-                }
-                prev_end = end;
-            }
+            check_frame_runs(f, off, fv_off, fv_node, fv_end, fv_idx, seen);
         }
         int64_t longest = 0;
-        for (int32_t p = 0; p < n_pairs; ++p)
+        for (int32_t p = 0; p < n_pairs; ++p) {
+            check_pair_frames(pairs, p, n_frames);
             for (int s = 0; s < 2; ++s) {
                 const int32_t f = pairs[2 * p + s];
-                if (f < 0 || f >= n_frames)
-                    throw Error(ORBFE_EINVAL, "pair " + std::to_string(p) + " names frame " + std::to_string(f) +
-                                                  ", which does not exist");
                 longest = std::max(longest, off[f + 1] - off[f]);
             }
+        }
         if (longest > out_stride) throw Error(ORBFE_EINVAL, "out_stride is shorter than a frame of the pairs");
         if (longest > 0 && (!out->match12 || !out->match21 || !out->bin12)) throw Error(ORBFE_EINVAL, "null argument");
         const int64_t n = off[n_frames], nn = fv_off[n_frames];
         Matcher& m = matcher();
         std::lock_guard<std::mutex> lk(m.mu);
-        if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : m.ev)
-            if (!e) HIPCK(hipEventCreate(&e));
-        hipStream_t s = m.stream;
+        hipStream_t s = m.t.get();
         const size_t np = (size_t)n_pairs, os = (size_t)out_stride;
         m.d_desc.ensure((size_t)n * 32);
         m.d_angle.ensure(n);
@@ -478,9 +444,9 @@ int orbfe_bow_match(const uint8_t* desc32, const float* angle, const uint8_t* el
         d.status = d.n_raw + np;
         d.bin12 = m.d_bin.p;
         HIPCK(hipMemsetAsync(d.status, 0, sizeof(int32_t), s));
-        HIPCK(hipEventRecord(m.ev[0], s));
+        m.t.begin(s);
         launch_match(fr, d_pairs, n_pairs, th, inclusive, nnratio, d, s);
-        HIPCK(hipEventRecord(m.ev[1], s));
+        m.t.end(s);
         // the blocks come back whole into staging; only the entries the kernel wrote, [0, n1) and [0, n2) of each
         // pair's block, reach the caller's arrays
         m.h_match.resize(2 * np * os);
@@ -493,7 +459,7 @@ int orbfe_bow_match(const uint8_t* desc32, const float* angle, const uint8_t* el
         HIPCK(hipMemcpyAsync(out->n_raw, d.n_raw, np * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (out->status) HIPCK(hipMemcpyAsync(out->status, d.status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
-        HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+        m.t.last_ms = m.t.elapsed_ms();
         for (size_t p = 0; p < np; ++p) {
             const size_t l1 = (size_t)(off[pairs[2 * p] + 1] - off[pairs[2 * p]]);
             const size_t l2 = (size_t)(off[pairs[2 * p + 1] + 1] - off[pairs[2 * p + 1]]);
@@ -511,7 +477,7 @@ int orbfe_bow_match_last_ms(float* ms) {
         if (!ms) throw Error(ORBFE_EINVAL, "null argument");
         Matcher& m = matcher();
         std::lock_guard<std::mutex> lk(m.mu);
-        *ms = m.last_ms;
+        *ms = m.t.last_ms;
     });
 }
 

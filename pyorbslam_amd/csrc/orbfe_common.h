@@ -1,6 +1,6 @@
 // orbfe_common.h — geometry tables shared by the host setup (orbfe_host.hip) and the gfx950 kernels
-// (orbfe_kernels.hip).  All tables are computed once per (extractor params, image size) on the host
-// with the reference's own float/double arithmetic and uploaded to device memory.
+// (orbfe_resize.hip, orbfe_detect.hip, orbfe_kernels.hip).  All tables are computed once per (extractor params,
+// image size) on the host with the reference's own float/double arithmetic and uploaded to device memory.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -71,6 +71,7 @@
 #include <string>
 #include <vector>
 
+#include "orbfe_device.h"
 #include "orbfe_host_util.h"
 
 using namespace orbfe;
@@ -445,10 +446,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                         if (!(fabs(chi - T) >= Echi + eps * T)) st = ORBFE_FUSE_MARGINAL;  // a NaN marks too
                         if (chi > T) continue;
                     }
-                    const uint4 da = desc[2 * f], db = desc[2 * f + 1];
-                    const unsigned d = __popc(da.x ^ qa.x) + __popc(da.y ^ qa.y) + __popc(da.z ^ qa.z) +
-                                       __popc(da.w ^ qa.w) + __popc(db.x ^ qb.x) + __popc(db.y ^ qb.y) +
-                                       __popc(db.z ^ qb.z) + __popc(db.w ^ qb.w);
+                    const unsigned d = hamming256(desc[2 * f], desc[2 * f + 1], qa, qb);
                     key = min(key, (d << 16) | (unsigned)pos);
                 }
             }
@@ -503,9 +501,7 @@ struct Searcher {
     std::vector<int32_t> h_i32;
     std::vector<uint8_t> h_st;
     std::vector<int64_t> h_chunk;  // k_sim3_search, k_fkf_search: (search, first item) per workgroup
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_ms = 0.f;
+    TimedStream t;
 };
 template <PsMode kMode>
 Searcher& searcher() {
@@ -514,14 +510,6 @@ Searcher& searcher() {
 }
 
 std::string at_kf(int32_t k, const std::string& what) { return "keyframe " + std::to_string(k) + ": " + what; }
-
-bool all_finite(const double* v, int64_t n) {
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // what orbfe_sim3_search and orbfe_fkf_search have besides the keyframes and the point table
 struct Sim3In {
@@ -635,7 +623,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
                  nl = (size_t)lvl_off[n_kf];
     // what only one variant stages has no room in the other's buffers
-    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kBlocked ? pad16(n) : 0;
+    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kBlocked ? pad_to(n, 16) : 0;
     const bool has_blocked = kBlocked && blocked != nullptr && n > 0;
     Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
@@ -651,19 +639,16 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
         n_chunk = m.h_chunk.size() / 2;
         if (n_chunk > 0x7FFFFFFFu) throw Error(ORBFE_EINVAL, "more items than one launch takes");
     }
-    if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : m.ev)
-        if (!e) HIPCK(hipEventCreate(&e));
-    hipStream_t s = m.stream;
+    hipStream_t s = m.t.get();
     // descriptors are read as uint4: both blocks start on 16 bytes
-    m.d_u8.ensure(pad16(n * 32) + pad16(np * 32) + n_blk + n_out);
+    m.d_u8.ensure(pad_to(n * 32, 16) + pad_to(np * 32, 16) + n_blk + n_out);
     m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 +
                    (kSim3 ? ns * ORBFE_SIM3_F64 : 0));
     m.d_i64.ensure(4 * (nk + 1) + (kRagged ? ns + 1 + 2 * n_chunk : 0));
     m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + 2 * n_out);
     uint8_t* d_desc = m.d_u8.p;
-    uint8_t* d_pdesc = d_desc + pad16(n * 32);
-    uint8_t* d_blk = d_pdesc + pad16(np * 32);
+    uint8_t* d_pdesc = d_desc + pad_to(n * 32, 16);
+    uint8_t* d_blk = d_pdesc + pad_to(np * 32, 16);
     uint8_t* d_st = d_blk + n_blk;
     double* d_kf = m.d_f64.p;
     double* d_xy = d_kf + nk * ORBFE_FUSE_KF_F64;
@@ -733,7 +718,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     kf.blocked = has_blocked ? d_blk : nullptr;
     const PsPts pt{d_pt, d_pdesc, n_pts};
     const PsOut d{d_bi, d_bd, d_st, out_stride};
-    HIPCK(hipEventRecord(m.ev[0], s));
+    m.t.begin(s);
     if constexpr (kRagged) {
         constexpr auto kernel = kSim3 ? k_sim3_search : k_fkf_search;
         hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx);
@@ -743,7 +728,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
         hipLaunchKernelGGL(kernel, dim3(chunks, (unsigned)n_kf), dim3(kPsChunk), 0, s, kf, pt, th, eps, d);
     }
     HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(m.ev[1], s));
+    m.t.end(s);
     // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
     // the caller's arrays
     m.h_i32.resize(2 * n_out);
@@ -751,7 +736,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, n_out, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
-    HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+    m.t.last_ms = m.t.elapsed_ms();
     if constexpr (kRagged) {  // every item was written
         std::memcpy(out->best_idx, m.h_i32.data(), n_out * sizeof(int32_t));
         std::memcpy(out->best_dist, m.h_i32.data() + n_out, n_out * sizeof(int32_t));
@@ -770,7 +755,7 @@ void last_ms(float* ms) {
     if (!ms) throw Error(ORBFE_EINVAL, "null argument");
     Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
-    *ms = m.last_ms;
+    *ms = m.t.last_ms;
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-// orbfe_kernels.h — launchers of the gfx950 kernels (orbfe_kernels.hip) used by orbfe_host.hip.
+// orbfe_kernels.h — launchers of the gfx950 kernels (orbfe_resize.hip, orbfe_detect.hip, orbfe_kernels.hip) used by
+// orbfe_host.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

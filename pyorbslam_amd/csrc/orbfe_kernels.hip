@@ -1,8 +1,7 @@
-// orbfe_kernels.hip — gfx950 (CDNA4) kernels of the ORB front-end hot path.
+// orbfe_kernels.hip — gfx950 (CDNA4) kernels of the ORB front-end hot path from the octree on, the kernels of no
+// stage (k_undistort, k_pack*, k_copy_segments) and the per-device LDS limits.  The pyramid (k_resize_*) is in
+// orbfe_resize.hip, FAST (k_detect) in orbfe_detect.hip, the device helpers the stages share in orbfe_device.h.
 //
-//   k_resize     cv::resize INTER_LINEAR 8U cascade (ComputePyramid, ORBextractor.cpp:1106-1132)
-//   k_detect     per-cell FAST-9/16 + 3x3 NMS + iniTh/minTh fallback + ordered compaction
-//                (ComputeKeyPointsOctTree cell loop, ORBextractor.cpp:768-828)
 //   k_octree     DistributeOctTree (ORBextractor.cpp:539-762), one workgroup per (level, image)
 //   k_orb        IC_Angle + GaussianBlur 7x7 (per keypoint neighbourhood) + steered BRIEF, one wavefront
 //                per keypoint (ORBextractor.cpp:77-147, 1074-1103)
@@ -21,7 +20,8 @@
 #include "orbfe_common.h"
 #include <type_traits>
 
-#include "orbfe_kernels.h"
+#include "orbfe_device.h"
+#include "orbfe_internal.h"
 
 namespace orbfe {
 
@@ -67,1101 +67,7 @@ __constant__ uint32_t c_bit_slots[256] = {
 #undef BRIEF_POINT
 #undef BRIEF_BIT
 
-// ------------------------------------------------------------------------------- small helpers
 typedef float df2 __attribute__((ext_vector_type(2)));  // packed f32 (v_pk_mul/fma/add_f32)
-
-// Buffer resource for a wave-uniform base pointer: loads take a 32-bit lane offset (no 64-bit address
-// arithmetic per lane).  Dword 3 = 0x00020000, the gfx9 raw-buffer format word.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0, 0x7FFFFFFF, 0x00020000);
-}
-
-// Buffer resource over the wave-uniform p, bounded to nbytes bytes.  The halves go through uint32_t: the
-// builtin returns int, and a sign-extended low half OR-ed into the 64-bit address corrupts its high bits
-// whenever bit 31 of the address is set.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bounded_rsrc(const void* p, uint32_t nbytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(nbytes), 0x00020000);
-}
-
-// Buffer resource over the dword-aligned address at or below the wave-uniform p, bounded to
-// bias + nbytes bytes; *bias = p's misalignment, so byte i of p sits at resource offset bias + i and a
-// dword-aligned load covering it starts at (bias + i) & ~3 (never below the resource base).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t aligned_rsrc(const void* p, uint32_t nbytes, uint32_t* bias) {
-    const uint64_t a = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    *bias = lo & 3u;
-    const uint32_t nb = __builtin_amdgcn_readfirstlane(nbytes);  // wave-uniform: an SGPR resource, never waterfalled
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)(((uint64_t)hi << 32) | (lo & ~3u)), 0, nb + (lo & 3u),
-                                             0x00020000);
-}
-
-// Wave-wide sum (wave-uniform result): DPP quad_perm / row_ror sums inside each 16-lane row, then the
-// four row sums through v_readlane (no LDS-crossbar round trips).
-// Two wave-wide sums at once: the DPP steps of the two interleave, so neither waits out the other's
-// VALU-write -> DPP-read hazard (the s_nop the compiler puts between dependent DPP adds).
-__device__ __forceinline__ void wave_sum2(int& a, int& b) {
-    a += __builtin_amdgcn_update_dpp(0, a, 0xB1, 0xF, 0xF, false);
-    b += __builtin_amdgcn_update_dpp(0, b, 0xB1, 0xF, 0xF, false);
-    a += __builtin_amdgcn_update_dpp(0, a, 0x4E, 0xF, 0xF, false);
-    b += __builtin_amdgcn_update_dpp(0, b, 0x4E, 0xF, 0xF, false);
-    a += __builtin_amdgcn_update_dpp(0, a, 0x124, 0xF, 0xF, false);
-    b += __builtin_amdgcn_update_dpp(0, b, 0x124, 0xF, 0xF, false);
-    a += __builtin_amdgcn_update_dpp(0, a, 0x128, 0xF, 0xF, false);
-    b += __builtin_amdgcn_update_dpp(0, b, 0x128, 0xF, 0xF, false);
-    a = __builtin_amdgcn_readlane(a, 0) + __builtin_amdgcn_readlane(a, 16) + __builtin_amdgcn_readlane(a, 32) +
-        __builtin_amdgcn_readlane(a, 48);
-    b = __builtin_amdgcn_readlane(b, 0) + __builtin_amdgcn_readlane(b, 16) + __builtin_amdgcn_readlane(b, 32) +
-        __builtin_amdgcn_readlane(b, 48);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false);  // row_ror:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);  // row_ror:8
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
-}
-
-__device__ __forceinline__ int reflect101(int p, int n) {
-    // one reflection suffices: every caller overshoots by less than n
-    p = p < 0 ? -p : p;
-    return p >= n ? 2 * n - 2 - p : p;
-}
-
-// cv::borderInterpolate(BORDER_REFLECT_101) for any overshoot: the reflection iterates (period 2 n - 2), a
-// 1-pixel side maps everything to 0 — the 19-pixel padding of levels up to 19 px (copyMakeBorder,
-// ORBextractor.cpp:1122-1128)
-__device__ __forceinline__ int reflect101_iter(int p, int n) {
-    if (n == 1) return 0;
-    const int per = 2 * n - 2;
-    p = (p < 0 ? -p : p) % per;
-    return p >= n ? per - p : p;
-}
-
-// the scalar tail of the vertical pass: FixedPtCast<int, uchar, 22> (round half up) of INTER_LINEAR, or for
-// the INTER_AREA fast path saturate_cast<uchar>(sum * 0.25f), i.e. sum / 4 rounded half to even (t = sum << 20)
-__device__ __forceinline__ uint32_t resize_tail(uint32_t t, int area) {
-    if (!area) return (t + (1u << 21)) >> 22;
-    const uint32_t q = t >> 22, r = t & 0x3FFFFFu;
-    return q + (r > 0x200000u || (r == 0x200000u && (q & 1u)));
-}
-
-__device__ __forceinline__ const uint8_t* level_ptr(const Geo& g, int l, const uint8_t* in, int64_t in_pitch,
-                                                    const uint8_t* ws, int img, int* stride) {
-    if (l == 0) {
-        *stride = g.W;
-        return in + (int64_t)img * in_pitch;
-    }
-    *stride = g.lv[l].pitch;
-    return ws + (int64_t)img * g.ws_bytes + g.lv[l].ws_off;
-}
-
-// A FAST cell's geometry as dword scalar loads (s_load) and SALU unpacking: reading the int16 fields
-// directly compiles to a per-lane global_load_ushort whose vmcnt wait also drains the next cell's ROI
-// prefetch — a full memory round trip per cell on the critical path.
-__device__ __forceinline__ CellGeo load_cell(const CellGeo* __restrict__ cells, int c) {
-    static_assert(sizeof(CellGeo) == 20, "CellGeo layout: 5 dwords");
-    const uint32_t* p = (const uint32_t*)(cells + c);
-    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3], w4 = p[4];
-    CellGeo cg;
-    cg.level = (int16_t)(w0 & 0xFFFFu);
-    cg.kw = (int16_t)(w0 >> 16);
-    cg.x0 = (int16_t)(w1 & 0xFFFFu);
-    cg.y0 = (int16_t)(w1 >> 16);
-    cg.x1 = (int16_t)(w2 & 0xFFFFu);
-    cg.y1 = (int16_t)(w2 >> 16);
-    cg.slot_off = (int)w3;
-    cg.slot_cap = (int)w4;
-    return cg;
-}
-
-// A packed level key's coordinates ((x + y * w) | score << 24, kKeyXYBits): y = mul_hi(xy, mag) >> sh is
-// floor(xy / w) for every xy < 2^24 (mag = ceil(2^(31 + s) / w), sh = s - 1, s = ceil(log2 w): the error term
-// xy * (mag * w - 2^(31 + s)) < 2^24 * w < 2^(31 + s)), then x = xy - y * w (both < 2^24: v_mad_u32_u24).
-struct KeyDiv {
-    uint32_t w, mag, sh;
-};
-__device__ __forceinline__ KeyDiv key_div(const LevelGeo& L) {
-    return KeyDiv{(uint32_t)__builtin_amdgcn_readfirstlane(L.w), (uint32_t)__builtin_amdgcn_readfirstlane((int)L.kmag),
-                  (uint32_t)__builtin_amdgcn_readfirstlane(L.ksh)};
-}
-__device__ __forceinline__ void key_xy(uint32_t k, KeyDiv kd, int& x, int& y) {
-    const uint32_t xy = k & 0xFFFFFFu;
-    const uint32_t q = __umulhi(xy, kd.mag) >> kd.sh;
-    y = (int)q;
-    x = (int)(xy - __umul24(q, kd.w));
-}
-
-// XCD-aware remap of a (gridDim.x, gridDim.y) grid.  Hardware block i (flattened, x fastest) runs on
-// XCD i % 8; the remap hands each XCD a contiguous run of logical blocks, so neighbouring tiles / cells /
-// bands — which share halo rows and partly used cache lines — meet in the same L2 instead of being
-// fetched from HBM by several XCDs.  Wave-uniform results (SGPRs).
-__device__ __forceinline__ void xcd_block(int& bx, int& by) {
-    const int nb = gridDim.x * gridDim.y, hw = blockIdx.y * gridDim.x + blockIdx.x, per = nb >> 3;
-    const int lb = hw < 8 * per ? (hw & 7) * per + (hw >> 3) : hw;
-    by = __builtin_amdgcn_readfirstlane(lb / (int)gridDim.x);
-    bx = __builtin_amdgcn_readfirstlane(lb - by * (int)gridDim.x);
-}
-
-// Block-wide exclusive scan of a[0..n) in LDS, in place; returns the total.  The first 256 threads own
-// contiguous chunks, so prefixes follow array order; further threads (blocks of up to 1024) only take
-// part in the barriers.  tmp: 257 ints of LDS.
-__device__ int block_excl_scan(int* a, int n, int* tmp) {
-    const int t = threadIdx.x;
-    const int per = (n + 255) >> 8;
-    const int b = t < 256 ? min(t * per, n) : n, e = min(b + per, n);
-    int s = 0;
-    for (int i = b; i < e; ++i) s += a[i];
-    if (t < 256) tmp[t] = s;
-    __syncthreads();
-    if (t < 64) {
-        const int v0 = tmp[4 * t], v1 = tmp[4 * t + 1], v2 = tmp[4 * t + 2], v3 = tmp[4 * t + 3];
-        const int tot = v0 + v1 + v2 + v3;
-        int inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(inc, o, 64);
-            if (t >= o) inc += y;
-        }
-        const int ex = inc - tot;
-        tmp[4 * t] = ex;
-        tmp[4 * t + 1] = ex + v0;
-        tmp[4 * t + 2] = ex + v0 + v1;
-        tmp[4 * t + 3] = ex + v0 + v1 + v2;
-        if (t == 63) tmp[256] = inc;
-    }
-    __syncthreads();
-    int run = t < 256 ? tmp[t] : 0;
-    for (int i = b; i < e; ++i) {
-        const int v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    const int total = tmp[256];
-    __syncthreads();
-    return total;
-}
-
-__device__ int block_sum(int v, int* red) {
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    int s = 0;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    __syncthreads();
-    return s;
-}
-
-// ------------------------------------------------------------------------------- k_resize
-// The per-level kernel (k_resize_rows) and the one-launch cascade (k_resize_cascade) share this scheme for a
-// band of output rows of level l (l >= 1), full width:
-//  * staging: the source rows the band reads (sy0(first) .. sy1(last) of level l-1) are one contiguous
-//    byte range in memory for every level (stride W for the input, the 16-byte pitch for derived levels),
-//    so they are copied to LDS as a flat run of aligned dwords, every load issued before the first wait;
-//    LDS byte sh0 + r * stride + c holds source row ys_lo + r, column c (sh0 = the range's misalignment).
-//  * the level's x coefficients become, per 4-pixel group, v_perm selectors into an 8-byte tap window
-//    starting at the group's first sx plus the packed (a0, a1) weights.
-//  * compute: per group and row, 2 x (3 LDS dwords, 2 v_alignbyte, 4 v_perm + 4 v_dot2_u32_u16) for the
-//    horizontal taps, then OpenCV's vertical rounding; one aligned dword store per 4 output pixels.
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-
-// Horizontal taps of a group's 4th pixel from a window of its own (LevelGeo::wide): A3 = LDS byte address of
-// its source pixel sx3, aa = its (a0, a1) weights.
-// (W3 = A3 - o the window's aligned address, o = A3 & 3: k_resize_rows hoists them out of its row loop)
-__device__ __forceinline__ uint32_t resize_tap3_al(uint32_t W3, uint32_t o, uint32_t aa) {
-    typedef __attribute__((address_space(3))) const uint32_t lds_c32;
-    lds_c32* w = (lds_c32*)(uintptr_t)W3;
-    const uint32_t x = __builtin_amdgcn_alignbyte(w[1], w[0], o);
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(x, x, 0x0c010c00u)),
-                                  __builtin_bit_cast(us2, aa), 0u, false);
-}
-__device__ __forceinline__ uint32_t resize_tap3(uint32_t A3, uint32_t aa) {
-    const uint32_t o = A3 & 3u;
-    return resize_tap3_al(A3 - o, o, aa);
-}
-constexpr int kRsSlots = 16;     // k_resize_cascade: staged dwords per thread per pass (it takes half)
-constexpr int kRsRowSlots = 24;  // k_resize_rows: staged dwords per thread per pass (a short pass takes 8 or 16)
-
-// k_resize_rows: one workgroup per band of LevelGeo::rs_rows output rows, the compute mapped so that a wave's
-// row is uniform.  The block holds R_s row sets of W_g waves (64 W_g >= the level's groups): lane
-// (w % W_g) * 64 + lane of a set owns one 4-pixel group for the whole band, its x selectors / weights in
-// registers; set w / W_g takes a run of consecutive rows of the band.  A row's source-row LDS addresses and
-// vertical weights come from scalar loads of the y table, the store is a buffer store with the row offset in
-// soffset: per 4 pixels only the taps, the vertical rounding and the pack are VALU work.  Blocks of
-// NT = 64 (W_g R_s + remainder wave) threads, 256 <= NT <= 512 (the host picks R_s).  AL4: the source row
-// stride is a multiple of 4 (every derived level's pitch, the input when its width is), so a group's window
-// has the same misalignment in every source row.
-template <bool MULTI, bool AL4, int NT>
-__global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t* __restrict__ in, int64_t in_pitch,
-                                                     uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
-                                                     const ResizeY* __restrict__ yt, int wg, int remw, int wgl,
-                                                     int* __restrict__ zero_word) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
-    // staged source rows; the staging's pointers carry their address spaces (generic ones compile to flat
-    // loads, which the compiler must wait for with vmcnt and lgkmcnt together)
-    typedef __attribute__((address_space(3))) uint32_t lds_w32;
-    typedef __attribute__((address_space(1))) const uint32_t glb_u32;
-    lds_w32* s_src = (lds_w32*)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)rs_lds;
-    const LevelGeo& L = g.lv[l];
-    const LevelGeo& P = g.lv[l - 1];
-    int bx, img;
-    xcd_block(bx, img);
-    const int t = threadIdx.x;
-    if (zero_word && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) *zero_word = 0;
-    const int rows = L.rs_rows;  // kRsRows, fewer for very wide levels (LevelGeo::rs_rows)
-    const int dy0 = bx * rows, nrow = min(rows, L.h - dy0);
-    const int ngrp = (L.w + 3) >> 2;
-    int sstride;
-    const uint8_t* src = level_ptr(g, l - 1, in, in_pitch, ws, img, &sstride);
-    const ResizeY* yb = yt + L.ytab_off + dy0;
-    const int ys_lo = yb[0].sy0, ys_hi = yb[nrow - 1].sy1;
-    const uintptr_t a0 = (uintptr_t)(src + (int64_t)ys_lo * sstride);
-    const int sh0 = (int)(a0 & 3);
-    glb_u32* gsrc = (glb_u32*)(a0 - sh0);
-    const int ndw = ((ys_hi - ys_lo) * sstride + P.w + sh0 + 3) >> 2;
-    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-    const uint32_t src_lds = (uint32_t)(uintptr_t)s_src;
-    // this thread's group: x selectors / weights straight from the table (issued with the staging loads)
-    // remw = 1: the last wave takes the groups past the wg full 64-group chunks (rem < 64 of them) for all
-    // rows of the band: lane j owns group wg * 64 + j % rem and rows j / rem, + 64 / rem, ... (a per-lane
-    // row), instead of a mostly idle row-uniform wave per row.  A set has wgl <= 8 waves: when a level has
-    // more chunks than that (rows wider than 2 048 px), a set's wave walks chunks c, c + wgl, ...
-    const int wv = t >> 6, fullw = NT / 64 - remw, nset = fullw / wgl;
-    const bool remwave = wv >= fullw;
-    const int set = __builtin_amdgcn_readfirstlane(remwave ? 0 : wv / wgl);
-    const int rem = ngrp - wg * 64, lane = t & 63;
-    const int rstep = remwave ? 64 / rem : nset;  // rows between a lane's rows in the remainder wave
-    const int row0 = remwave ? lane / rem : set;
-    int ch = remwave ? wg : wv - set * wgl;       // this wave's first 64-group chunk
-    const int ch_step = remwave ? 1 : wgl, ch_end = remwave ? wg + 1 : wg;
-    int grp = 0;
-    bool own = false;
-    uint4 e{}, aa{};
-    int sx0 = 0;
-    uint32_t d3 = 0;  // LevelGeo::wide: the 4th pixel's source column past the group's first
-    auto chunk = [&](int c) {
-        grp = remwave ? wg * 64 + lane % rem : c * 64 + lane;
-        own = remwave ? lane < rstep * rem : grp < ngrp;
-        if (own) {
-            const uint4* xg = (const uint4*)(xt + L.xtab_off);
-            const uint4 q0 = xg[2 * grp], q1 = xg[2 * grp + 1];
-            sx0 = (int)q0.x;
-            d3 = q1.z - q0.x;
-            auto sel = [&](uint32_t sx) { const uint32_t r = sx - q0.x; return r | ((r + 1) << 16) | 0x0c000c00u; };
-            e = uint4{sel(q0.x), sel(q0.z), sel(q1.x), sel(q1.z)};
-            aa = uint4{q0.y, q0.w, q1.y, q1.w};
-        }
-    };
-    chunk(ch);
-    // staging by every thread of the block: compile-time strides (NT), immediate LDS offsets, and every load of
-    // a pass (up to kRsRowSlots dwords per thread; KITTI's bands take one pass, level 1 its 21 slots) issued
-    // before the first wait.  The loads go through a wave-uniform buffer resource: one VGPR offset for all
-    // slots, the slot and pass in the SGPR offset, no 64-bit address arithmetic; the range test is one compare
-    // of the thread index against a wave-uniform limit per slot, shared by the load and the LDS store.  The
-    // test must guard the load itself: the resource's bounds check does not include the SGPR offset, so an
-    // unguarded slot past the run reads past the buffer.
-    {
-        const __amdgpu_buffer_rsrc_t rsrc = bounded_rsrc((const void*)(uintptr_t)gsrc, (uint32_t)(4 * ndw));
-        // one pass: S slots per thread, every load before the first LDS store
-        auto pass = [&](auto nslot, int base, int left) {
-            constexpr int S = decltype(nslot)::value;
-            uint32_t v[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                v[k] = 0u;
-                if (t < left - NT * k)
-                    v[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (uint32_t)(4 * t), (uint32_t)(4 * (base + NT * k)), 0);
-            }
-            // one LDS address per pass (immediate offsets per slot)
-            lds_w32* sp = s_src + base + t;
-#pragma unroll
-            for (int k = 0; k < S; ++k)
-                if (t < left - NT * k) sp[NT * k] = v[k];
-        };
-        for (int base = 0; base < ndw; base += NT * kRsRowSlots) {
-            const int left = ndw - base;  // wave-uniform: a scalar branch picks the pass's slot count
-            if (left <= NT * kRsRowSlots / 3)
-                pass(std::integral_constant<int, kRsRowSlots / 3>{}, base, left);
-            else if (left <= NT * (kRsRowSlots * 2 / 3))
-                pass(std::integral_constant<int, kRsRowSlots * 2 / 3>{}, base, left);
-            else
-                pass(std::integral_constant<int, kRsRowSlots>{}, base, left);
-        }
-    }
-    __syncthreads();
-    uint8_t* dst = ws + (int64_t)img * g.ws_bytes + L.ws_off + (int64_t)dy0 * L.pitch;
-    const __amdgpu_buffer_rsrc_t rd = uniform_rsrc(dst);
-    for (;;) {
-        if (!own) return;  // only a level's last chunk is partial
-        const int dx = 4 * grp;
-        const bool tail = dx + 3 >= L.xvec;  // FixedPtCast<int, uchar, 22> past the last SIMD block
-        const uint32_t lsrc = src_lds + (uint32_t)sh0 + (uint32_t)sx0;
-        // AL4: the window's misalignment and aligned base, the same in every source row of the band
-        const uint32_t lo = lsrc & 3u, lal = lsrc - lo, lo3 = (lsrc + d3) & 3u, lal3 = lsrc + d3 - lo3;
-        // TAIL: a wave with a lane in the scalar tail (a level's last groups), or the remainder wave, keeps the
-        // taps unmasked for resize_tail and tests each lane per row; every other wave masks a source row's taps
-        // once, where they are produced (reused taps would be masked twice), and packs without the test
-        auto band = [&](auto tail_c) {
-            constexpr bool TAIL = decltype(tail_c)::value;
-            // psy: the previous row's second source row.  Full waves walk consecutive rows, and a row's first
-            // source row is mostly the previous row's second: its taps are reused, not recomputed.  The two tap
-            // sets alternate between ha and hb over a 2-row unrolled loop, so the reuse needs no register copies
-            // (4-5 v_mov per row and 4-pixel group before)
-            int psy = -1;
-            auto row = [&](int rr, uint32_t (&h0)[4], uint32_t (&h1)[4], bool reuse) {
-                const ResizeY y = yb[rr];  // full waves: uniform, scalar loads
-                const uint32_t r0 = (uint32_t)((y.sy0 - ys_lo) * sstride), r1 = (uint32_t)((y.sy1 - ys_lo) * sstride);
-                const uint32_t B0 = (uint32_t)y.b0 << 12, B1 = (uint32_t)y.b1 << 12;
-                auto taps = [&](uint32_t roff, uint32_t (&h)[4]) {
-                    const uint32_t A = lsrc + roff, o = AL4 ? lo : A & 3u;
-                    lds_u32* w = (lds_u32*)(uintptr_t)(AL4 ? lal + roff : A - o);
-                    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-                    const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o);
-                    h[0] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.x)),
-                                                  __builtin_bit_cast(us2, aa.x), 0u, false);
-                    h[1] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.y)),
-                                                  __builtin_bit_cast(us2, aa.y), 0u, false);
-                    h[2] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.z)),
-                                                  __builtin_bit_cast(us2, aa.z), 0u, false);
-                    h[3] = L.wide ? (AL4 ? resize_tap3_al(lal3 + roff, lo3, aa.w) : resize_tap3(A + d3, aa.w))
-                                  : __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.w)),
-                                                           __builtin_bit_cast(us2, aa.w), 0u, false);
-                    if (!TAIL) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) h[k] &= ~15u;
-                    }
-                };
-                // h0 holds the taps of source row psy (the previous row's h1) when reuse applies
-                if (!(reuse && y.sy0 == psy)) taps(r0, h0);
-                taps(r1, h1);
-                if (reuse) psy = y.sy1;
-                uint32_t out;
-                if (TAIL) {
-                    uint32_t v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = (__umulhi(h0[k] & ~15u, B0) + __umulhi(h1[k] & ~15u, B1) + 2) >> 2;
-                    if (tail) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (dx + k >= L.xvec) v[k] = resize_tail(h0[k] * (B0 >> 12) + h1[k] * (B1 >> 12), L.area);
-                    }
-                    out = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-                } else {
-                    // the sums + 2 are below 2^10: two to a dword at 16-bit spacing, one shift for both, one v_perm
-                    // for the four bytes (5 instructions for 7)
-                    uint32_t s[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s[k] = __umulhi(h0[k], B0) + __umulhi(h1[k], B1);
-                    const uint32_t p01 = ((s[1] << 16) + (s[0] + 0x20002u)) >> 2, p23 = ((s[3] << 16) + (s[2] + 0x20002u)) >> 2;
-                    out = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-                }
-                // pixels past L.w land in the row's pitch padding
-                __builtin_amdgcn_raw_buffer_store_b32(out, rd, (uint32_t)dx, (uint32_t)(rr * L.pitch), 0);
-            };
-            uint32_t ha[4] = {0u, 0u, 0u, 0u}, hb[4] = {0u, 0u, 0u, 0u};
-            if (!(TAIL && remwave)) {  // set s: rows [s * per, (s + 1) * per), consecutive
-                const int per = (nrow + nset - 1) / nset, rend = min(set * per + per, nrow);
-                int rr = set * per;
-                for (; rr + 1 < rend; rr += 2) {
-                    row(rr, ha, hb, true);
-                    row(rr + 1, hb, ha, true);
-                }
-                if (rr < rend) row(rr, ha, hb, true);
-            } else {
-                for (int rr = row0; rr < nrow; rr += rstep) row(rr, ha, hb, false);
-            }
-        };
-        // wave-uniform (the ballot is over the lanes still here: the chunk's owners)
-        if (__builtin_amdgcn_ballot_w64(tail || remwave) != 0)
-            band(std::true_type{});
-        else
-            band(std::false_type{});
-        if (!MULTI) return;  // one chunk per wave (every level up to 2 048 px)
-        ch += ch_step;
-        if (ch >= ch_end) return;
-        chunk(ch);
-    }
-}
-
-// k_resize_cascade: the whole pyramid (levels 1 .. L-1) in ONE launch for small batches, where the seven
-// per-level launches are seven latency chains of a few microseconds each (8 pairs: 58 us of 233 per step).
-// One 512-thread workgroup per (horizontal strip, image).  Strip s computes at every level the rows the
-// next level's rows of the strip need (its own rows, plus a halo its neighbours also compute) and stores
-// the rows it owns; ownership partitions every level (host: resize_strips), so each output row is written
-// exactly once, with the arithmetic of k_resize_rows (same taps, same vertical rounding).  Level 0's source
-// rows are staged from the input like k_resize_rows; every later level reads the previous level's strip
-// from LDS, ping-ponging between two buffers (A: level 0 staging and even levels, B: odd levels).
-// tab: per (strip, level) int16 {computed lo, hi, owned lo, hi}; offB / offX: byte offsets of buffer B and
-// of the per-level x selector table in the dynamic LDS.
-constexpr int kCasNT = 1024;  // threads per strip workgroup
-__global__ __launch_bounds__(kCasNT) void k_resize_cascade(Geo g, const uint8_t* __restrict__ in, int64_t in_pitch,
-                                                        uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
-                                                        const ResizeY* __restrict__ yt, const int16_t* __restrict__ tab,
-                                                        int offB, int offX, int* __restrict__ zero_word,
-                                                        long long* __restrict__ prof) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
-    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-    typedef __attribute__((address_space(3))) uint32_t lds_w32;
-    const int strip = blockIdx.x, img = blockIdx.y, t = threadIdx.x, lane = t & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(t >> 6), nwv = blockDim.x >> 6;
-    if (zero_word && strip == 0 && img == 0 && t == 0) *zero_word = 0;
-    // orbfe_debug_cascade_profile: wall-clock marks of the first thread, 32 per (image, strip): 0 start,
-    // 1 staging issued + stored, 2 + l level l's rows may start (after its first barrier), 12 + l level l done
-    long long* pm = prof ? prof + ((int64_t)img * gridDim.x + strip) * 32 : nullptr;
-    auto mark = [&](int id) {
-        if (pm && t == 0) pm[id] = (long long)wall_clock64();
-    };
-    mark(0);
-    const int L = g.nlevels;
-    const int16_t* st = tab + (int64_t)strip * L * 4;
-    const uint32_t baseA = (uint32_t)(uintptr_t)(lds_u32*)rs_lds;
-    const uint32_t baseB = baseA + (uint32_t)offB;
-    // per group: v_perm selectors, then (a0, a1) weights; its first source column — double-buffered by level
-    // parity: level l + 1's entries are loaded into registers while level l computes.  Every LDS and global
-    // access goes through an address-space-qualified pointer: a generic one (an array of LDS pointers indexed
-    // by the level's parity) compiles to flat loads, which count in vmcnt too — the item loop then waited for
-    // the previous item's global stores before each table read.
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) v4u lds_u4;
-    typedef __attribute__((address_space(3))) int lds_i32;
-    typedef __attribute__((address_space(1))) const v4u glb_u4;
-    auto u4 = [](v4u v) { return uint4{v.x, v.y, v.z, v.w}; };
-    typedef __attribute__((address_space(1))) const uint32_t glb_u32;
-    auto s_xa_of = [&](int par) { return (lds_u4*)(uintptr_t)(baseA + (uint32_t)offX + (uint32_t)(par * 32 * g.rs_ngrp)); };
-    auto s_sx_of = [&](int par) {
-        return (lds_i32*)(uintptr_t)(baseA + (uint32_t)offX + (uint32_t)(64 * g.rs_ngrp + par * 4 * g.rs_ngrp));
-    };
-    constexpr int kPre = 1024 / kCasNT;  // groups per thread held in registers (levels up to 4 096 px)
-    uint4 pq0[kPre], pq1[kPre];
-    auto prefetch = [&](int l) {
-        if (l >= g.nlevels) return;
-        glb_u4* xg = (glb_u4*)(xt + g.lv[l].xtab_off);
-        const int ng = (g.lv[l].w + 3) >> 2;
-#pragma unroll
-        for (int k = 0; k < kPre; ++k) {
-            const int gi = t + kCasNT * k;
-            if (gi < ng) {
-                pq0[k] = u4(xg[2 * gi]);
-                pq1[k] = u4(xg[2 * gi + 1]);
-            }
-        }
-    };
-    auto commit = [&](int l) {
-        lds_u4* sxa = s_xa_of(l & 1);
-        lds_i32* ssx = s_sx_of(l & 1);
-        const int ng = (g.lv[l].w + 3) >> 2;
-#pragma unroll
-        for (int k = 0; k < kPre; ++k) {
-            const int gi = t + kCasNT * k;
-            if (gi < ng) {
-                const uint4 q0 = pq0[k], q1 = pq1[k];
-                auto sel = [&](uint32_t sx) { const uint32_t r = sx - q0.x; return r | ((r + 1) << 16) | 0x0c000c00u; };
-                sxa[2 * gi] = v4u{sel(q0.x), sel(q0.z), sel(q1.x), sel(q1.z)};
-                sxa[2 * gi + 1] = v4u{q0.y, q0.w, q1.y, q1.w};
-                ssx[gi] = (int)(q0.x | ((q1.z - q0.x) << 24));  // sx0, and the 4th pixel's offset (wide levels)
-            }
-        }
-    };
-    prefetch(1);
-    // ---- level 0 rows the strip's level 1 needs, staged as a flat dword run (k_resize_rows' staging)
-    uint32_t src_base = baseA, src_sh;
-    int src_row0, src_stride;
-    {
-        const LevelGeo& L1 = g.lv[1];
-        const ResizeY* yb = yt + L1.ytab_off;
-        const int c0 = st[4], c1 = st[5];
-        const int ys_lo = yb[c0].sy0, ys_hi = yb[c1 - 1].sy1;
-        const uintptr_t a0 = (uintptr_t)(in + (int64_t)img * in_pitch + (int64_t)ys_lo * g.W);
-        src_sh = (uint32_t)(a0 & 3);
-        glb_u32* gsrc = (glb_u32*)(a0 - src_sh);
-        const int ndw = ((ys_hi - ys_lo) * g.W + g.W + (int)src_sh + 3) >> 2;
-        lds_w32* s_src = (lds_w32*)(uintptr_t)baseA;
-        for (int base = 0; base < ndw; base += kCasNT * kRsSlots / 2) {
-            uint32_t v[kRsSlots / 2];
-#pragma unroll
-            for (int k = 0; k < kRsSlots / 2; ++k) {
-                const int i = base + t + kCasNT * k;
-                v[k] = i < ndw ? gsrc[i] : 0u;
-            }
-#pragma unroll
-            for (int k = 0; k < kRsSlots / 2; ++k) {
-                const int i = base + t + kCasNT * k;
-                if (i < ndw) s_src[i] = v[k];
-            }
-        }
-        src_row0 = ys_lo;
-        src_stride = g.W;
-    }
-    mark(1);
-    for (int l = 1; l < L; ++l) {
-        const LevelGeo& Lv = g.lv[l];
-        const int c0 = st[4 * l], c1 = st[4 * l + 1], o0 = st[4 * l + 2], o1 = st[4 * l + 3];
-        const int ngrp = (Lv.w + 3) >> 2, nch = (ngrp + 63) >> 6;
-        // x selectors / weights of the level (k_resize's per-group form), loaded during the previous level
-        commit(l);
-        prefetch(l + 1);
-        const lds_u4* s_xa = s_xa_of(l & 1);
-        const lds_i32* s_sx0 = s_sx_of(l & 1);
-        const ResizeY* yb = yt + Lv.ytab_off;
-        const uint32_t dst_base = (l & 1) ? baseB : baseA;
-        __syncthreads();  // selectors staged; the source rows complete (previous level / staging)
-        mark(2 + l);
-        uint8_t* gdst = ws + (int64_t)img * g.ws_bytes + Lv.ws_off;
-        const int pitch = Lv.pitch;
-        // the level's fields in registers (read from the kernel arguments once, not per item)
-        const int lv_wide = __builtin_amdgcn_readfirstlane(Lv.wide), lv_xvec = __builtin_amdgcn_readfirstlane(Lv.xvec),
-                  lv_area = __builtin_amdgcn_readfirstlane(Lv.area);
-        // items (row, chunk), row-major; wave wv takes items wv, wv + nwv, ...: row / chunk advanced
-        // incrementally (uniform), no division per item.  (Measured slower here: k_resize_rows' row sets — a
-        // wave walks consecutive rows of one chunk, reusing the previous row's taps — 39 -> 43 us at 8 pairs,
-        // and two items per step with both items' reads issued before either waits, 39 -> 49 us.)
-        // items = rows: wave wv takes rows c0 + wv, + nwv, ...; per row its y entry and offsets once (scalar),
-        // then every 64-group chunk of the row (a uniform loop).  Measured (tools/cascade_profile.py, traces
-        // at 8 pairs): (row, chunk) items 39.7 us, rows 36.4; also tried and slower: row sets with the previous
-        // row's taps reused (43), two items per step with all reads issued first (49), the y entries staged in
-        // LDS instead of scalar loads (42).
-        for (int r = c0 + wv; r < c1; r += nwv) {
-            const ResizeY y = yb[r];
-            const uint32_t r0 = (uint32_t)((y.sy0 - src_row0) * src_stride), r1 = (uint32_t)((y.sy1 - src_row0) * src_stride);
-            const uint32_t B0 = (uint32_t)y.b0 << 12, B1 = (uint32_t)y.b1 << 12;
-            const bool own = r >= o0 && r < o1;
-            const uint32_t lrow = dst_base + (uint32_t)((r - c0) * pitch);
-            uint8_t* grow = gdst + (int64_t)r * pitch;
-            for (int ch = 0; ch < nch; ++ch) {
-                const int grp = ch * 64 + lane;
-                if (grp < ngrp) {
-                    const uint4 e = u4(s_xa[2 * grp]), aa = u4(s_xa[2 * grp + 1]);
-                    const int sxp = s_sx0[grp];
-                    const uint32_t d3 = (uint32_t)sxp >> 24;
-                    const uint32_t lsrc = src_base + src_sh + (uint32_t)(sxp & 0xFFFFFF);
-                    auto taps = [&](uint32_t roff, uint32_t (&h)[4]) {
-                        const uint32_t A = lsrc + roff, o = A & 3u;
-                        lds_u32* w = (lds_u32*)(uintptr_t)(A - o);
-                        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-                        const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, w0, o), d1 = __builtin_amdgcn_alignbyte(w2, w1, o);
-                        h[0] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.x)),
-                                                      __builtin_bit_cast(us2, aa.x), 0u, false);
-                        h[1] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.y)),
-                                                      __builtin_bit_cast(us2, aa.y), 0u, false);
-                        h[2] = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.z)),
-                                                      __builtin_bit_cast(us2, aa.z), 0u, false);
-                        h[3] = lv_wide ? resize_tap3(A + d3, aa.w)
-                                       : __builtin_amdgcn_udot2(__builtin_bit_cast(us2, __builtin_amdgcn_perm(d1, d0, e.w)),
-                                                                __builtin_bit_cast(us2, aa.w), 0u, false);
-                    };
-                    uint32_t h0[4], h1[4];
-                    taps(r0, h0);
-                    taps(r1, h1);
-                    const int dx = 4 * grp;
-                    uint32_t v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = (__umulhi(h0[k] & ~15u, B0) + __umulhi(h1[k] & ~15u, B1) + 2) >> 2;
-                    if (dx + 3 >= lv_xvec) {  // FixedPtCast<int, uchar, 22> past the last SIMD block
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (dx + k >= lv_xvec) v[k] = resize_tail(h0[k] * (B0 >> 12) + h1[k] * (B1 >> 12), lv_area);
-                    }
-                    const uint32_t px = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-                    *(lds_w32*)(uintptr_t)(lrow + (uint32_t)dx) = px;
-                    if (own) *(uint32_t*)(grow + dx) = px;  // pitch padding past w
-                }
-            }
-        }
-        src_base = dst_base;
-        src_sh = 0;
-        src_row0 = c0;
-        src_stride = pitch;
-        __syncthreads();  // this level's rows complete before the next level reads them / the selectors change
-        mark(12 + l);
-    }
-}
-
-// ------------------------------------------------------------------------------- k_detect
-// One wavefront per (cell, image).  FAST "M" of a pixel:
-//   M = max(v - min_arc max9, max_arc min9 - v) over the 16 arcs of 9 contiguous circle pixels;
-//   the pixel is a segment-test corner at threshold t iff M > t, and OpenCV's cornerScore is M - 1.
-// Work is done on horizontal pixel pairs (x, x + 1), x even, in packed f16: pixel values live in LDS as
-// u16 0x3C00 | p, normal f16 numbers in [1, 2) ordered exactly like p, so v_pk_maximum3/minimum3_f16
-// are exact and differences of the raw u16 bits are differences of p.
-//  1. ROI -> LDS (u16, pitch RP, ROI column c at index c + 1 so even window columns are dword
-//     aligned): 16 lanes per row each read one dword from the 4-byte aligned start of column -1, take
-//     the next dword from the neighbour lane (DPP), re-align with v_alignbyte and widen with v_perm; the
-//     next cell's loads are in flight during this cell's compute.
-//  2. Pre-test, every pair: P = max(v - min_k max(c_k, c_k+1), max_k min(c_k, c_k+1) - v) over the
-//     circularly adjacent cardinal pairs (circle points 0, 4, 8, 12) bounds M from above, because every
-//     arc of 9 contains such a pair (computed as max(v - max(min(c0, c2), min(c1, c3)), ...): every
-//     cycle edge joins an even and an odd cardinal).  Pairs with P <= tq = min(iniTh, minTh) in both pixels have M <= tq:
-//     neither corners nor relevant NMS neighbours at either threshold; they keep M = 0.  The others are
-//     queued in row-major order (ballot + mbcnt).  (Queueing single pixels halves the M work per pixel
-//     but not per cell: a cell's queue is a few 64-entry steps either way, measured slower.)
-//  3. Exact M of the queued pairs -> a u8 M map with a zero border (half the LDS of a u16 map: detect is
-//     occupancy-bound, one 64-thread workgroup per wave); pairs with a pixel above max(tq, 1) are
-//     compacted in place into the same queue (row-major) for NMS.
-//  4. NMS over that queue, two pixels per lane.  For t >= 1, "score > every 8-neighbour's score at t" (neighbours outside the
-//     window or not corners at t score 0) is equivalent to M > t and M > max(8-neighbour M): a neighbour
-//     with M <= t is below M anyway.  So the local-max test is threshold independent: one pass decides
-//     iniTh and minTh together, and the iniTh -> minTh fallback (ORBextractor.cpp:811-815) only picks
-//     which survivor list is kept.  Kept pixels are written in the queue's row-major order, i.e.
-//     cv::FAST's output order.
-typedef _Float16 fd_h2 __attribute__((ext_vector_type(2)));
-typedef short fd_s2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ fd_h2 fd_h(uint32_t v) { return __builtin_bit_cast(fd_h2, v); }
-__device__ __forceinline__ fd_s2 fd_s(fd_h2 v) { return __builtin_bit_cast(fd_s2, v); }
-__device__ __forceinline__ fd_h2 fd_max(fd_h2 a, fd_h2 b) { return __builtin_elementwise_maximum(a, b); }
-__device__ __forceinline__ fd_h2 fd_min(fd_h2 a, fd_h2 b) { return __builtin_elementwise_minimum(a, b); }
-__device__ __forceinline__ fd_h2 fd_max3(fd_h2 a, fd_h2 b, fd_h2 c) { return fd_max(fd_max(a, b), c); }
-__device__ __forceinline__ fd_h2 fd_min3(fd_h2 a, fd_h2 b, fd_h2 c) { return fd_min(fd_min(a, b), c); }
-template <int DX>
-__device__ __forceinline__ fd_h2 fd_pair(const uint32_t* q) {  // u16 pair at column offset DX
-    if constexpr ((DX & 1) == 0) return fd_h(q[DX / 2]);
-    else return fd_h(__builtin_amdgcn_alignbyte(q[(DX + 1) / 2], q[(DX - 1) / 2], 2));
-}
-
-// Upper bounds of the two adjacent pixel pairs at dwords R and R + 1 (pixels x .. x + 3), sharing the
-// cardinal rows: 6 dwords of the centre row, 2 above, 2 below.
-template <int S>
-__device__ __forceinline__ void fast_bound_quad(const uint32_t* R, fd_s2& bA, fd_s2& bB) {
-    const uint32_t m2 = R[-2], m1 = R[-1], z0 = R[0], p1 = R[1], p2 = R[2], p3 = R[3];
-    const uint32_t u0 = R[-3 * S], u1 = R[-3 * S + 1], d0 = R[3 * S], d1 = R[3 * S + 1];
-    auto bound = [](uint32_t v, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
-        const fd_h2 h0 = fd_h(c0), h1 = fd_h(c1), h2 = fd_h(c2), h3 = fd_h(c3);
-        // min over the 4 cycle edges (i, i + 1) of max(h_i, h_i+1): every edge joins an even and an odd
-        // cardinal, so it is max(min(h0, h2), min(h1, h3)) (3 ops instead of 6); dually for b
-        const fd_h2 a = fd_max(fd_min(h0, h2), fd_min(h1, h3));
-        const fd_h2 b = fd_min(fd_max(h0, h2), fd_max(h1, h3));
-        const fd_s2 vs = __builtin_bit_cast(fd_s2, v);
-        return __builtin_elementwise_max(vs - fd_s(a), fd_s(b) - vs);
-    };
-    // cardinals in circle order: 0 = (0, +3), 4 = (+3, 0), 8 = (0, -3), 12 = (-3, 0)
-    bA = bound(z0, d0, __builtin_amdgcn_alignbyte(p2, p1, 2), u0, __builtin_amdgcn_alignbyte(m1, m2, 2));
-    bB = bound(p1, d1, __builtin_amdgcn_alignbyte(p3, p2, 2), u1, __builtin_amdgcn_alignbyte(z0, m1, 2));
-}
-
-// Exact M of the pixel pair at dword R (row stride S dwords), as biased u16 x2.
-template <int S>
-__device__ __forceinline__ uint32_t fast_m_pair(const uint32_t* R) {
-    const fd_h2 p[16] = {fd_pair<0>(R + 3 * S),  fd_pair<1>(R + 3 * S),  fd_pair<2>(R + 2 * S),  fd_pair<3>(R + S),
-                         fd_pair<3>(R),          fd_pair<3>(R - S),      fd_pair<2>(R - 2 * S),  fd_pair<1>(R - 3 * S),
-                         fd_pair<0>(R - 3 * S),  fd_pair<-1>(R - 3 * S), fd_pair<-2>(R - 2 * S), fd_pair<-3>(R - S),
-                         fd_pair<-3>(R),         fd_pair<-3>(R + S),     fd_pair<-2>(R + 2 * S), fd_pair<-1>(R + 3 * S)};
-    fd_h2 mx3[16], mn3[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        mx3[k] = fd_max3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]);
-        mn3[k] = fd_min3(p[k], p[(k + 1) & 15], p[(k + 2) & 15]);
-    }
-    fd_h2 lo = fd_max3(mx3[0], mx3[3], mx3[6]), hi = fd_min3(mn3[0], mn3[3], mn3[6]);
-#pragma unroll
-    for (int k = 1; k < 15; k += 2) {
-        lo = fd_min3(lo, fd_max3(mx3[k], mx3[(k + 3) & 15], mx3[(k + 6) & 15]),
-                     fd_max3(mx3[k + 1], mx3[(k + 4) & 15], mx3[(k + 7) & 15]));
-        hi = fd_max3(hi, fd_min3(mn3[k], mn3[(k + 3) & 15], mn3[(k + 6) & 15]),
-                     fd_min3(mn3[k + 1], mn3[(k + 4) & 15], mn3[(k + 7) & 15]));
-    }
-    lo = fd_min(lo, fd_max3(mx3[15], mx3[2], mx3[5]));
-    hi = fd_max(hi, fd_min3(mn3[15], mn3[2], mn3[5]));
-    const fd_s2 v = __builtin_bit_cast(fd_s2, R[0]);
-    const fd_s2 m = __builtin_elementwise_max(__builtin_elementwise_max(v - fd_s(lo), fd_s(hi) - v), fd_s2{0, 0});
-    return __builtin_bit_cast(uint32_t, m) | 0x3C003C00u;
-}
-
-__device__ __forceinline__ int imax3(int a, int b, int c) { return max(max(a, b), c); }
-
-// o +/- (this lane's bit of the lane mask m): one v_addc / v_subb with the mask as the carry (the compiler's
-// form of o + (int)inverse_ballot(m) is a v_cndmask and an add)
-__device__ __forceinline__ int fd_plus_bit(int o, uint64_t m) {
-    int r;
-    uint64_t co;
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r), "=s"(co) : "v"(o), "s"(m));
-    return r;
-}
-__device__ __forceinline__ int fd_minus_bit(int o, uint64_t m) {
-    int r;
-    uint64_t co;
-    asm("v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r), "=s"(co) : "v"(o), "s"(m));
-    return r;
-}
-
-// cells per k_detect wavefront: 4 (the next cell's ROI loads overlap this one), or 1 for batches too small to
-// give the chip >= 8 waves per CU that way (a frame pair: 610 waves of 4 cells, 2 440 of one)
-constexpr int kFdCells = 4;
-constexpr int kFdSmallCells = 1;  // cells per wave for small batches
-
-template <bool B>
-struct fd_flag {  // a compile-time switch passed to a generic lambda
-    static constexpr bool value = B;
-};
-
-__device__ __forceinline__ int lanes_below(uint64_t b) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
-}
-
-// u16 elements of k_detect's ROI area: the ROI itself, and after the M stage the minTh survivors of a cell
-// (u32 records, at most slot_cap = Geo::fd_alt); a multiple of 8 so the M map after it is 16-byte aligned
-__host__ __device__ inline int detect_roi_elems(const Geo& g, int rp) {
-    const int n = rp * g.max_rh > 2 * g.fd_alt ? rp * g.max_rh : 2 * g.fd_alt;
-    return (n + 7) & ~7;
-}
-
-// RP: ROI pitch in u16 (48, 64 or 96; >= widest ROI + 3).  NS: staged row slots (4 rows each, >= max_rh / 4).
-// CPW: cells per wave.  ST: the debug counters of orbfe_debug_detect_stats / orbfe_debug_detect_lanes.
-// 5 waves per SIMD (<= 96 VGPRs; 4 for the wider / taller ROI shapes, which need the registers) and
-// <= 8 KiB of LDS for KITTI / EuRoC cells: detect is bound by how many
-// cells are in flight per CU (16 -> 10 resident waves costs +32 %, measured by padding the launch's LDS).
-template <int RP, int NS, int CPW, bool ST = false>
-__global__ __launch_bounds__(64, (RP == 48 && NS <= 12) ? 5 : 4) void k_detect(Geo g, const CellGeo* __restrict__ cells, const uint8_t* __restrict__ in,
-                                               int64_t in_pitch, const uint8_t* __restrict__ ws,
-                                               int* __restrict__ cell_count, uint32_t* __restrict__ slots,
-                                               int* __restrict__ stats) {
-    constexpr int S = RP / 2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    // ROI (max_rh rows x RP u16); after the M stage the same bytes stage the minTh survivors (u32 records)
-    uint16_t* roi = (uint16_t*)lds;
-    // u8 M map, (max_wh + 2) rows of MP = RP bytes: px (x, y) at (y + 1) * MP + x + 2, i.e. at the pair's queue
-    // entry + MP
-    constexpr int MP = RP;
-    uint8_t* mm = (uint8_t*)(roi + detect_roi_elems(g, RP));
-    // pair queue: entry = y * RP + x + 2 (x even; fd_pq entries), the ROI u16 index of the dword that holds
-    // the top-left corner of the pair's circles (ROI row y = window row y - 3, pair at ROI index
-    // entry + 3 RP + 2), so the M stage's ROI reads are the entry plus non-negative immediate offsets and its map
-    // address the entry plus MP; the M stage compacts the queue in place into the NMS queue
-    uint16_t* pq = (uint16_t*)(mm + MP * (g.max_wh + 2));
-    int bx, img;
-    xcd_block(bx, img);  // neighbouring cells' ROIs overlap by 6 rows / columns: keep them in one L2
-    const int lane = threadIdx.x;
-    const int c_first = bx * CPW, c_last = min(c_first + CPW, g.ncells);
-    // ROI staging, 8 lanes per row (dwords 2d, 2d + 1), 8 rows per step (NS / 2 steps): lane d loads two
-    // dwords of the row from the 4-byte aligned start of column -1 and takes dword 2d + 2 from its
-    // neighbour lane (DPP row_shl:1) to re-align 8 bytes with v_alignbyte (rows are <= 59 px, so 16
-    // dwords cover every row; what lane 7 receives from the next row's lane only lands in columns >= 60).
-    // The loads of the next cell are issued before this cell's compute (prefetch into NS registers).
-    constexpr int NS2 = NS / 2;
-    const int d = lane & 7, r0 = lane >> 3;
-    uint2 raw[NS2];
-    // Every slot loads unconditionally, through a resource bounded to the level (a row past it reads 0): rows
-    // past the ROI and dwords past its width land only in LDS the commit below never writes or in columns
-    // past the ROI, and the per-slot range tests, zero fills and branches are gone (one v_add per slot)
-    auto issue = [&](int c) {
-        const CellGeo cg = load_cell(cells, c);
-        int stride;
-        const uint8_t* lvl = level_ptr(g, cg.level, in, in_pitch, ws, img, &stride);
-        const __amdgpu_buffer_rsrc_t rs = bounded_rsrc(lvl, (uint32_t)(stride * g.lv[cg.level].h));
-        const uint32_t lvl_lo = (uint32_t)(uintptr_t)lvl;
-        const uint32_t off0 = (uint32_t)((cg.y0 + r0) * stride + cg.x0 - 1);
-        // rows r0 + 8 k share the alignment of row r0 (8 k * stride is a multiple of 4)
-        const uint32_t al0 = off0 - ((lvl_lo + off0) & 3u) + 8u * d;
-#pragma unroll
-        for (int k = 0; k < NS2; ++k)
-            raw[k] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs, al0 + (uint32_t)(8 * k * stride), 0, 0));
-    };
-    if (c_first < c_last) issue(c_first);
-    for (int c = c_first; c < c_last; ++c) {
-        const CellGeo cg = load_cell(cells, c);
-        const int rw = cg.x1 - cg.x0, rh = cg.y1 - cg.y0;
-        const int ww = rw - 6, wh = rh - 6;  // detection window = ROI rows/cols 3 .. n-4
-        {
-            int stride;
-            const uint8_t* lvl = level_ptr(g, cg.level, in, in_pitch, ws, img, &stride);
-            const uint32_t lvl_lo = (uint32_t)(uintptr_t)lvl;
-            const uint32_t off0 = (uint32_t)((cg.y0 + r0) * stride + cg.x0 - 1);
-            const int n8 = (rw + 8) >> 3;  // 8-column groups of columns -1 .. rw-1 (8 * n8 <= RP)
-#pragma unroll
-            for (int k = 0; k < NS2; ++k) {
-                // every lane takes part in the DPP (uniform control flow); lanes 15 of a DPP row get 0 (bound_ctrl:
-                // the same 0 as an `old` operand, without the v_mov that would materialise it)
-                const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)raw[k].x, 0x101, 0xF, 0xF, true);
-                const int r = r0 + 8 * k;
-                if (r < rh && d < n8) {
-                    const int sh = (int)((lvl_lo + off0 + (uint32_t)(8 * k * stride)) & 3u);
-                    const uint32_t w0 = __builtin_amdgcn_alignbyte(raw[k].y, raw[k].x, sh);
-                    const uint32_t w1 = __builtin_amdgcn_alignbyte(nb, raw[k].y, sh);
-                    uint4 u;
-                    u.x = __builtin_amdgcn_perm(0x3C3C3C3Cu, w0, 0x04010400u);
-                    u.y = __builtin_amdgcn_perm(0x3C3C3C3Cu, w0, 0x04030402u);
-                    u.z = __builtin_amdgcn_perm(0x3C3C3C3Cu, w1, 0x04010400u);
-                    u.w = __builtin_amdgcn_perm(0x3C3C3C3Cu, w1, 0x04030402u);
-                    *(uint4*)(roi + r * RP + 8 * d) = u;
-                }
-            }
-            // the M map with its zero border
-            uint4* m128 = (uint4*)mm;
-            for (int i = lane; i < (MP / 16) * (wh + 2); i += 64) m128[i] = uint4{0u, 0u, 0u, 0u};
-        }
-        if (c + 1 < c_last) issue(c + 1);  // in flight during this cell's compute
-        __syncthreads();
-        auto process = [&]() {
-            if (ww <= 0 || wh <= 0) {
-                if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = 0;
-                return;
-            }
-        const int tq = min(g.ini_th, g.min_th);
-        // ---- 2. pre-test, two adjacent pairs (pixels x .. x + 3) per lane and step, quads in row-major
-        //         order (lane -> quad i0 + lane); the pair queue stays row-major (two ballots per step)
-        const int qrow = (ww + 3) >> 2, nquad = qrow * wh;
-        // n / qrow for n <= 64 without an integer division: (n + 0.5) / qrow is >= 0.5 / qrow >= 1/28 away
-        // from an integer, far more than the reciprocal's error
-        const float rq = __builtin_amdgcn_rcpf((float)qrow);
-        auto div_q = [&](int n) { return (int)__builtin_fmaf((float)n, rq, 0.5f * rq); };
-        const int step_y = div_q(64), step_x = 64 - step_y * qrow;
-        // Two queues when minTh < iniTh (ORBextractor.cpp:795-815: FAST at iniTh, then minTh only for a
-        // cell where iniTh found nothing): B = pairs whose bound exceeds minTh (from the front of pq), and
-        // its subset A = bound above iniTh (from the back, growing down).  Exact M, NMS and output run on A
-        // first; B is processed only for a cell that A leaves empty.  A pixel outside every A pair has
-        // M <= bound <= iniTh, so it can neither be an iniTh corner nor beat one in the NMS: the iniTh pass
-        // needs M of the A pairs only.  Should the two queues meet (a cell where more than half of the pairs
-        // pass at minTh), the cell takes the one-pass path below instead (both thresholds over B).
-        const bool two = g.min_th < g.ini_th;
-        const int tA = two ? g.ini_th : 0x7fff;  // above every bound
-        const int cap = g.fd_pq;
-        int npq = 0, npa = 0;
-        {
-            // two 64-quad steps per iteration: both steps' ROI reads are issued before either waits
-            // (one LDS round trip per 128 quads); lanes past the window read a clamped row and vote 0
-            int qy = div_q(lane), qx = lane - qy * qrow;
-            auto advance = [&](int& y, int& x) {
-                y += step_y;
-                x += step_x;
-                if (x >= qrow) {
-                    x -= qrow;
-                    ++y;
-                }
-            };
-            // the pass conditions as lane masks (v_cmp straight into SGPR pairs, combined on the SALU): a
-            // bool per lane would cost a v_cndmask + v_cmp round trip per ballot.  Only the last quad of a
-            // row can hold pixels past the window (x4 == xl); rem = ww - xl of its 4 are inside.
-            const int xl = 4 * (qrow - 1), rem = ww - xl;
-            auto gt = [](int a, int b) { return (uint64_t)__builtin_amdgcn_sicmp(a, b, 38); };  // ICMP_SGT
-            auto bound_at = [&](const uint32_t* R, uint64_t in, uint64_t last, uint64_t& ca, uint64_t& cb, uint64_t& aa,
-                                uint64_t& ab) {
-                fd_s2 ba, bb;
-                fast_bound_quad<S>(R, ba, bb);
-                const uint64_t va = rem > 1 ? ~0ull : ~last, vb2 = rem > 2 ? ~0ull : ~last,
-                               vb3 = rem > 3 ? ~0ull : ~last;
-                ca = in & (gt(ba.x, tq) | (gt(ba.y, tq) & va));
-                cb = in & vb2 & (gt(bb.x, tq) | (gt(bb.y, tq) & vb3));
-                aa = ca & (gt(ba.x, tA) | (gt(ba.y, tA) & va));
-                ab = cb & (gt(bb.x, tA) | (gt(bb.y, tA) & vb3));
-            };
-            auto bound = [&](int i, int y, int x4, uint64_t& ca, uint64_t& cb, uint64_t& aa, uint64_t& ab) {
-                bound_at((const uint32_t*)(roi + (min(y, wh - 1) + 3) * RP + x4 + 4),
-                         __builtin_amdgcn_sicmp(i, nquad, 40), __builtin_amdgcn_sicmp(x4, xl, 32), ca, cb, aa, ab);
-            };
-            // entries in lane order, a lane's first before its second: the lane's first goes after every entry
-            // of the lanes below it (one mbcnt chain over both masks, seeded with the queue length), its second
-            // one further when it has a first
-            auto below2 = [](uint64_t m0, uint64_t m1, int base) {
-                return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1,
-                       __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, base))));
-            };
-            auto emit = [&](int n, uint64_t b0, uint64_t b1, uint64_t a0, uint64_t a1) {
-                const bool ca = __builtin_amdgcn_inverse_ballot_w64(b0), cb = __builtin_amdgcn_inverse_ballot_w64(b1);
-                const uint16_t e = (uint16_t)n;
-                const int o = below2(b0, b1, npq);
-                if (ca) pq[o] = e;
-                if (cb) pq[fd_plus_bit(o, b0)] = (uint16_t)(e + 2);
-                npq += __popcll(b0) + __popcll(b1);
-                // a half without an A pair (more than half of them) leaves npa and the collide rule as they are:
-                // the A emission (two inverse ballots, an mbcnt chain, two address chains and stores) runs under
-                // one scalar test
-                {   // one threshold: tA is out of reach, the A masks are empty
-                    const int na = __popcll(a0) + __popcll(a1);
-                    if (ST && lane == 0 && two && na == 0) atomicAdd(&stats[6], 1);
-                    // both counts only grow: once the queues would meet they stay met (collide below), and A
-                    // stops writing so that B stays intact for the one-pass path
-                    if (na != 0 && npq + npa + na <= cap) {
-                        const bool aa = __builtin_amdgcn_inverse_ballot_w64(a0), ab = __builtin_amdgcn_inverse_ballot_w64(a1);
-                        const int oa = cap - 1 - below2(a0, a1, npa);
-                        if (aa) pq[oa] = e;
-                        if (ab) pq[fd_minus_bit(oa, a0)] = (uint16_t)(e + 2);
-                    }
-                    npa += na;
-                }
-            };
-            if (qrow <= 8) {
-                // rows of 8 lanes (every KITTI / EuRoC cell but EuRoC level 7's): lane 8 r + qx takes quad qx
-                // of row y0 + r (lanes qx >= qrow idle), so the lane order is the row-major queue order and
-                // the ROI address and the entry are per-lane constants plus a uniform row offset.  Lanes of
-                // rows past the window read (and vote 0 on) rows below it: still inside the LDS allocation
-                // (ROI rows, then the M map).
-                const int r = lane >> 3, qx = lane & 7;
-                const uint64_t colok = __builtin_amdgcn_sicmp(qx, qrow, 40), last = __builtin_amdgcn_sicmp(4 * qx, xl, 32);
-                const uint32_t* R0 = (const uint32_t*)(roi + (r + 3) * RP + 4 * qx + 4);
-                for (int y0 = 0; y0 < wh; y0 += 16) {
-                    uint64_t ca0, cb0, ca1, cb1, aa0, ab0, aa1, ab1;
-                    bound_at(R0 + y0 * S, colok & __builtin_amdgcn_sicmp(r, wh - y0, 40), last, ca0, cb0, aa0, ab0);
-                    bound_at(R0 + (y0 + 8) * S, colok & __builtin_amdgcn_sicmp(r, wh - y0 - 8, 40), last, ca1, cb1, aa1,
-                             ab1);
-                    emit((y0 + r) * RP + 4 * qx + 2, ca0, cb0, aa0, ab0);
-                    emit((y0 + r + 8) * RP + 4 * qx + 2, ca1, cb1, aa1, ab1);
-                }
-            } else {
-                for (int i0 = 0; i0 < nquad; i0 += 128) {
-                    int qy2 = qy, qx2 = qx;
-                    advance(qy2, qx2);
-                    uint64_t ca0, cb0, ca1, cb1, aa0, ab0, aa1, ab1;
-                    bound(i0 + lane, qy, 4 * qx, ca0, cb0, aa0, ab0);
-                    bound(i0 + 64 + lane, qy2, 4 * qx2, ca1, cb1, aa1, ab1);
-                    emit(qy * RP + 4 * qx + 2, ca0, cb0, aa0, ab0);
-                    emit(qy2 * RP + 4 * qx2 + 2, ca1, cb1, aa1, ab1);
-                    qy = qy2;
-                    qx = qx2;
-                    advance(qy, qx);
-                }
-            }
-        }
-        __syncthreads();
-        // ---- 3. exact M of a queue's pairs -> M map; the pairs with a pixel above tl are compacted in place
-        //         (entry i at qb[dir * i]: dir -1 for A at the back of pq) into the NMS queue; returns its length
-        //         The stage takes the entries [first, n) and appends to the nn entries the queue already holds
-        //         (nn <= first).  With a carry (the A queue only), the kb lanes that the last step leaves idle take
-        //         the B entries pq[0 .. kb): they store their M too and compact the pairs with a pixel above
-        //         max(minTh, 1) in place into pq[0 .. nnb), outside the stage's own compaction (a pair of both
-        //         queues would otherwise enter A's NMS queue twice); kb <= those idle lanes, so only the last step
-        //         carries.
-        auto m_stage = [&](auto carry, uint16_t* qb, int dir, int first, int n, int nn, int tl, int kb, int& nnb) {
-            constexpr bool CY = decltype(carry)::value;
-            const int ne = CY ? n + kb : n;  // entries that have a lane
-            auto slot = [&](int i) { return CY && i >= n ? pq + (i - n) : qb + dir * i; };
-            // the queue entry of the next step is read one step ahead (its LDS round trip overlaps this step)
-            uint32_t e_next = first + lane < ne ? *slot(first + lane) : 2u;  // idle lanes: pixel (0, 0)
-            for (int k0 = first; k0 < n; k0 += 64) {
-                // every lane computes (a lane past ne repeats an earlier entry of its own, harmlessly); the map
-                // store and the compaction take the lanes of this step's entries (lane masks, as the pre-test)
-                const uint32_t e = e_next;
-                if (k0 + 64 + lane < ne) e_next = *slot(k0 + 64 + lane);
-                const uint64_t inr = __builtin_amdgcn_sicmp(k0 + lane, n, 40);  // ICMP_SLT
-                const uint64_t ine = CY ? (uint64_t)__builtin_amdgcn_sicmp(k0 + lane, ne, 40) : inr;
-                const uint32_t m = fast_m_pair<S>((const uint32_t*)(roi + e) + 3 * S + 1);
-                // the u8 map keeps M itself (low byte of each biased half); odd width: the last pair's second
-                // pixel lies outside the window, its map entry is cleared after this stage
-                if (__builtin_amdgcn_inverse_ballot_w64(ine))
-                    *(uint16_t*)(mm + e + MP) = (uint16_t)__builtin_amdgcn_perm(0u, m, 0x0c0c0200u);
-                // slots below k0 + 64 are written; every read of the queue (this step's entries, the next
-                // step's prefetch) was issued before
-                auto above = [&](int t) {
-                    return (uint64_t)__builtin_amdgcn_sicmp((int)(m & 0x3FFu), t, 38) |
-                           (uint64_t)__builtin_amdgcn_sicmp((int)((m >> 16) & 0x3FFu), t, 38);
-                };
-                const uint64_t bh = inr & above(tl);
-                if (__builtin_amdgcn_inverse_ballot_w64(bh)) qb[dir * (nn + lanes_below(bh))] = (uint16_t)e;
-                nn += __popcll(bh);
-                if (CY && (ine & ~inr) != 0) {  // the carried lanes: their entries pq[0 .. kb) are all read
-                    const uint64_t bc = ine & ~inr & above(max(g.min_th, 1));
-                    if (__builtin_amdgcn_inverse_ballot_w64(bc)) pq[nnb + lanes_below(bc)] = (uint16_t)e;
-                    nnb += __popcll(bc);
-                }
-            }
-            // odd width: column ww (right of the window) got the outside pixel's M from the last pairs; NMS
-            // reads it as a neighbour (and as that pixel's own score) and needs 0 there
-            if ((ww & 1) && lane < wh) mm[(lane + 1) * MP + ww + 2] = 0;
-            __syncthreads();
-            return nn;
-        };
-        // ---- 4. NMS (local max) over an NMS queue + ordered compaction.  For t >= 1, "score > every
-        //         8-neighbour's score at t" is M > t and M > max(neighbour M) (a neighbour with M <= t is
-        //         below anyway).  Kept pixels: pairs row-major, pixel x before x + 1 = cv::FAST's order.
-        //         thb1 >= 1: also test the second threshold and stage its survivors in `alt` (one-pass path).
-        uint32_t* out = slots + (int64_t)img * g.slot_total + cg.slot_off;
-        uint32_t* alt = (uint32_t*)roi;  // >= 2 * slot_cap u16 (detect_roi_elems)
-        auto nms_stage = [&](const uint16_t* qb, int dir, int nn, int thb0, int thb1, int& t0, int& t1) {
-            t0 = t1 = 0;
-            for (int k0 = 0; k0 < nn; k0 += 64) {
-                // every lane computes on an entry in range; lane masks select the kept pixels
-                const uint64_t inr = __builtin_amdgcn_sicmp(k0 + lane, nn, 40);  // ICMP_SLT
-                const int e = qb[dir * min(k0 + lane, nn - 1)];
-                const uint8_t* q = mm + e + MP;  // pixel A = (x, y); B = (x + 1, y)
-                const int t_0 = q[-MP - 1], t_1 = q[-MP], t_2 = q[-MP + 1], t_3 = q[-MP + 2];
-                const int m_0 = q[-1], owna = q[0], ownb = q[1], m_3 = q[2];
-                const int b_0 = q[MP - 1], b_1 = q[MP], b_2 = q[MP + 1], b_3 = q[MP + 2];
-                const int c1 = max(t_1, b_1), c2 = max(t_2, b_2);  // the pair's columns without its own row
-                const int na = max(imax3(t_0, m_0, b_0), imax3(c1, c2, ownb));
-                const int nb = max(imax3(t_3, m_3, b_3), imax3(c1, c2, owna));
-                // (x + 3, y + 3) = (e % RP + 1, e / RP + 3)
-                const uint32_t xy = (uint32_t)(cg.x0 + (int)((uint32_t)e % RP) + 1) +
-                                    __umul24((uint32_t)(cg.y0 + (int)((uint32_t)e / RP) + 3), (uint32_t)cg.kw);
-                const uint32_t reca = xy | ((uint32_t)(owna - 1) << 24);
-                const uint32_t recb = (xy + 1u) | ((uint32_t)(ownb - 1) << 24);
-                auto keep = [&](int th, uint64_t& ba, uint64_t& bb, int& t, uint32_t* dst) {
-                    ba = inr & (uint64_t)__builtin_amdgcn_sicmp(owna, max(na, th), 38);
-                    bb = inr & (uint64_t)__builtin_amdgcn_sicmp(ownb, max(nb, th), 38);
-                    const bool ka = __builtin_amdgcn_inverse_ballot_w64(ba), kb = __builtin_amdgcn_inverse_ballot_w64(bb);
-                    const int o = t + lanes_below(ba) + lanes_below(bb);
-                    // slot_cap holds by the strict NMS (no two kept pixels are 8-neighbours); never write past it
-                    if (ka && o < cg.slot_cap) dst[o] = reca;
-                    if (kb) {
-                        const int ob = fd_plus_bit(o, ba);
-                        if (ob < cg.slot_cap) dst[ob] = recb;
-                    }
-                    t += __popcll(ba) + __popcll(bb);
-                };
-                uint64_t ba, bb;
-                keep(thb0, ba, bb, t0, out);
-                if (thb1 > 0) keep(thb1, ba, bb, t1, alt);
-            }
-        };
-        const bool collide = npq + npa > cap;
-        // orbfe_debug_detect_stats: cells that took the one-pass path despite two thresholds (the queues met)
-        if (ST && lane == 0 && two && collide) atomicAdd(&stats[1], 1);
-        int total = 0;
-        if (two && !collide) {
-            int t0, t1;
-            // A's last M step has 64 ceil(npa / 64) - npa idle lanes (on average nine tenths of the step): they take
-            // the first kb entries of B.  Such an entry outside A has M <= bound <= iniTh in both pixels, so its map
-            // entry (0 until now) changes neither A's compaction nor the iniTh NMS; an entry of both queues stores
-            // the same M twice.  The fallback then starts behind the carried entries, on their nnb0 <= kb survivors
-            // (the front of pq and the A region at its back are disjoint: npq + npa <= cap).
-            const int kb = min(((npa + 63) & ~63) - npa, npq);
-            int nnb0 = 0, none = 0;
-            const int nna = m_stage(fd_flag<true>{}, pq + cap - 1, -1, 0, npa, 0, max(tA, 1), kb, nnb0);
-            if (ST && lane == 0 && kb > 0) {
-                atomicAdd(&stats[3], 1);
-                atomicAdd(&stats[4], kb);
-            }
-            nms_stage(pq + cap - 1, -1, nna, max(g.ini_th, 1), 0, t0, t1);
-            total = t0;
-            if (t0 == 0) {  // minTh fallback: the rest of B (the A pairs' M is recomputed, identically)
-                if (ST && lane == 0) {
-                    atomicAdd(&stats[2], 1);
-                    atomicAdd(&stats[5], (npq - kb + 63) >> 6);
-                }
-                const int nnb = m_stage(fd_flag<false>{}, pq, 1, kb, npq, nnb0, max(g.min_th, 1), 0, none);
-                nms_stage(pq, 1, nnb, max(g.min_th, 1), 0, t0, t1);
-                total = t0;
-            }
-        } else {
-            // one pass over B at tq = min(iniTh, minTh), both thresholds in the NMS: iniTh survivors go
-            // straight out, minTh survivors are staged in the (dead) ROI area and copied out only if iniTh
-            // kept nothing
-            int none = 0;
-            const int nnq = m_stage(fd_flag<false>{}, pq, 1, 0, npq, 0, max(tq, 1), 0, none);
-            const bool fb = g.min_th != g.ini_th;
-            int t0, t1;
-            nms_stage(pq, 1, nnq, max(g.ini_th, 1), fb ? max(g.min_th, 1) : 0, t0, t1);
-            total = t0;
-            if (t0 == 0 && t1 > 0) {
-                __syncthreads();
-                for (int i = lane; i < min(t1, cg.slot_cap); i += 64) out[i] = alt[i];
-                total = t1;
-            }
-        }
-        if (lane == 0) cell_count[(int64_t)img * g.ncells + c] = min(total, cg.slot_cap);
-        if (ST && lane == 0) atomicAdd(&stats[0], 1);
-        };
-        process();
-        __syncthreads();  // the next cell overwrites the ROI and the M map
-    }
-}
 
 // ------------------------------------------------------------------------------- k_octree
 // DistributeOctTree as a sequence of data-parallel passes.  The std::list of the reference is held as
@@ -1735,34 +641,6 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1, 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2, 3
     return v;
-}
-__device__ __forceinline__ int wave_total_dpp(int v) { return __builtin_amdgcn_readlane(wave_incl_scan_dpp(v), 63); }
-// wave maximum of non-negative values, in every lane
-__device__ __forceinline__ int wave_max_dpp(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// Exclusive scan, in place, of a list held lane-major in registers (lane l holds elements l N .. l N + N - 1);
-// returns the total.
-template <int N>
-__device__ __forceinline__ int chunk_excl_scan(int (&v)[N]) {
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const int x = v[k];
-        v[k] = s;
-        s += x;
-    }
-    const int inc = wave_incl_scan_dpp(s);
-    const int ex = inc - s;
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] += ex;
-    return __builtin_amdgcn_readlane(inc, 63);
 }
 
 // NB rounds of one key per lane (the atomics of all rounds after their scans), its bin b (0xFFFFFFFF: no key)
@@ -3764,6 +2642,7 @@ __global__ __launch_bounds__(256) void k_stereo(Geo g, StereoArgs A) {
                 const int oct = __float_as_int(ri[j].y);
                 const bool ok = iR[j] >= 0 && oct >= kl.octave - 1 && oct <= kl.octave + 1 && minU <= ri[j].x &&
                                 (double)ri[j].x <= (double)kl.x;
+                // written out, not hamming256(): the call changes this loop's schedule
                 const uint32_t dist = __popc(a0.x ^ b0[j].x) + __popc(a0.y ^ b0[j].y) + __popc(a0.z ^ b0[j].z) +
                                       __popc(a0.w ^ b0[j].w) + __popc(a1.x ^ b1[j].x) + __popc(a1.y ^ b1[j].y) +
                                       __popc(a1.z ^ b1[j].z) + __popc(a1.w ^ b1[j].w);
@@ -3980,9 +2859,7 @@ __global__ __launch_bounds__(256) void k_hamming_matrix(const uint8_t* __restric
     if (j >= nb) return;
     const uint4* A4 = (const uint4*)(a + (int64_t)i * 32);
     const uint4* B4 = (const uint4*)(b + (int64_t)j * 32);
-    const uint4 a0 = A4[0], a1 = A4[1], b0 = B4[0], b1 = B4[1];
-    out[(int64_t)i * nb + j] = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                               __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+    out[(int64_t)i * nb + j] = (int)hamming256(A4[0], A4[1], B4[0], B4[1]);
 }
 
 // Candidate-list search: one wavefront per query; keeps the two smallest (dist, position) pairs in
@@ -4002,9 +2879,7 @@ __global__ __launch_bounds__(256) void k_hamming_search(const uint8_t* __restric
     int d1 = 256, p1 = 0x7fffffff, d2 = 256, p2 = 0x7fffffff;
     for (int pos = b + lane; pos < e; pos += 64) {
         const uint4* T4 = (const uint4*)(tr + (int64_t)idx[pos] * 32);
-        const uint4 b0 = T4[0], b1 = T4[1];
-        const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                      __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+        const int d = (int)hamming256(a0, a1, T4[0], T4[1]);
         if (all_d) all_d[pos] = d;
         if (d < d1) {
             d2 = d1; p2 = p1; d1 = d; p1 = pos;
@@ -4037,90 +2912,6 @@ __global__ __launch_bounds__(256) void k_hamming_search(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------- launchers
-template <bool AL4>
-static auto resize_rows_kernel(int threads) {
-    switch (threads) {
-        case 256: return k_resize_rows<false, AL4, 256>;
-        case 320: return k_resize_rows<false, AL4, 320>;
-        case 384: return k_resize_rows<false, AL4, 384>;
-        case 448: return k_resize_rows<false, AL4, 448>;
-        default: return k_resize_rows<false, AL4, 512>;
-    }
-}
-
-hipError_t launch_resize(const Geo& g, int l, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
-                         const ResizeY* yt, int n_images, hipStream_t s, bool remainder_wave, int* zero_word) {
-    const LevelGeo& L = g.lv[l];  // LDS sized for this level (its bands' source rows)
-    dim3 grid((L.h + L.rs_rows - 1) / L.rs_rows, n_images);
-    // k_resize_rows against the round-2 item-mapped kernel (profiles/r03/resize_rows_ab_r3f.log): 414 -> 394 us
-    // per 256 pairs standalone, +0.8 % on the 4-handle step.
-    // a level whose groups leave a last chunk of fewer than 40 (of 64) takes it in one remainder wave
-    // (remainder_wave = false: never, every chunk row-uniform); at most 8 waves per row set, each walking several
-    // chunks on rows wider than 2 048 px, so the block stays within __launch_bounds__(512)
-    const int ngrp = (L.w + 3) / 4, rem = ngrp % 64;
-    const int wg0 = (ngrp + 63) / 64;
-    const int remw = (remainder_wave && ngrp >= 64 && wg0 <= 8 && rem > 0 && rem < 40) ? 1 : 0;
-    const int wg = remw ? ngrp / 64 : wg0;
-    const int wgl = std::min(wg, 8 - remw);
-    const int sets = std::max(1, (4 - remw + wgl - 1) / wgl);  // >= 256 threads per block
-    const int threads = 64 * (wgl * sets + remw);
-    if (threads < 256 || threads > 512) return hipErrorInvalidConfiguration;
-    // MULTI: a wave walks several 64-group chunks (levels wider than 2 048 px; always 8 waves, one set); the
-    // one-chunk form is instantiated apart (the loop around it cost 3 % on KITTI, tools/dbg/mb_ab.sh, round 4),
-    // per block size (the staging's strides) and per alignment of the source row stride
-    const bool al4 = (l >= 2 ? g.lv[l - 1].pitch : g.W) % 4 == 0;
-    const auto k = wg > wgl ? (al4 ? k_resize_rows<true, true, 512> : k_resize_rows<true, false, 512>)
-                            : (al4 ? resize_rows_kernel<true>(threads) : resize_rows_kernel<false>(threads));
-    hipLaunchKernelGGL(k, grid, dim3(threads), (size_t)L.rs_nsrc * L.rs_sp + 16, s, g, l, in, in_pitch, ws, xt, yt, wg,
-                       remw, wgl, zero_word);
-    return hipGetLastError();
-}
-
-int detect_rp(const Geo& g) { return g.max_rw + 3 <= 48 ? 48 : g.max_rw + 3 <= 64 ? 64 : 96; }
-
-size_t detect_lds_bytes(const Geo& g) {
-    // ROI, the M map (pitch RP bytes), the pair queue
-    return 2 * (size_t)detect_roi_elems(g, detect_rp(g)) + (size_t)detect_rp(g) * (g.max_wh + 2) + 2 * (size_t)g.fd_pq;
-}
-
-// cells per wave for a batch: 4 unless that leaves fewer than 8 waves per CU
-int detect_cpw(const Geo& g, int n_images) {
-    // 8 pairs: 39 us with one cell per wave against 47 with four (tools/microbench.py, round 4)
-    return n_images < kSmallBatchImages || (int64_t)n_images * ((g.ncells + kFdCells - 1) / kFdCells) < 8 * 256
-               ? kFdSmallCells
-               : kFdCells;
-}
-
-template <int RP, int NS>
-static void launch_detect_rp(const Geo& g, const CellGeo* cells, const uint8_t* in, int64_t in_pitch, const uint8_t* ws,
-                             int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int cpw, int* stats) {
-    const dim3 grid((g.ncells + cpw - 1) / cpw, n_images), blk(64);
-    const size_t lds = detect_lds_bytes(g);
-    auto k = stats ? (cpw == kFdSmallCells ? k_detect<RP, NS, kFdSmallCells, true> : k_detect<RP, NS, kFdCells, true>)  // debug counters
-                   : (cpw == kFdSmallCells ? k_detect<RP, NS, kFdSmallCells> : k_detect<RP, NS, kFdCells>);
-    hipLaunchKernelGGL(k, grid, blk, lds, s, g, cells, in, in_pitch, ws, cell_count, slots, stats);
-}
-
-hipError_t launch_detect(const Geo& g, const CellGeo* cells, const uint8_t* in, int64_t in_pitch, const uint8_t* ws,
-                         int* cell_count, uint32_t* slots, int n_images, hipStream_t s, int cells_per_wave, int* stats) {
-    const int cpw = cells_per_wave ? cells_per_wave : detect_cpw(g, n_images);
-    if (cpw != kFdCells && cpw != kFdSmallCells) return hipErrorInvalidValue;
-    // ROIs of at most 48 rows (KITTI, EuRoC) stage from 12 registers, taller ones (<= 64) from 16
-    const bool tall = g.max_rh > 48;
-    switch (detect_rp(g)) {
-        case 48:
-            if (tall) launch_detect_rp<48, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
-            else launch_detect_rp<48, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
-            break;
-        case 64:
-            if (tall) launch_detect_rp<64, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
-            else launch_detect_rp<64, 12>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
-            break;
-        default: launch_detect_rp<96, 16>(g, cells, in, in_pitch, ws, cell_count, slots, n_images, s, cpw, stats);
-    }
-    return hipGetLastError();
-}
-
 size_t octree_lds_bytes(const Geo& g, int maxcell) {
     const int NC = g.max_ncap;
     int pow2 = 1;
@@ -4161,7 +2952,7 @@ static LdsAttr* lds_attr() {
     return &g_lds[dev];
 }
 
-static hipError_t raise_lds(const void* fn, int bytes) {
+hipError_t raise_lds(const void* fn, int bytes) {
     std::lock_guard<std::mutex> lk(g_lds_mu);
     LdsAttr* a = lds_attr();
     if (!a) return hipErrorInvalidDevice;
@@ -4172,14 +2963,11 @@ static hipError_t raise_lds(const void* fn, int bytes) {
     return e;
 }
 
-// the limit raised on the current device for kernel fn
-static int lds_limit(const void* fn) {
+int lds_limit(const void* fn) {
     std::lock_guard<std::mutex> lk(g_lds_mu);
     const LdsAttr* a = lds_attr();
     return a ? a->get(fn) : 0;
 }
-
-hipError_t prepare_resize_cascade(int lds_bytes) { return raise_lds((const void*)k_resize_cascade, lds_bytes); }
 
 // k_octree_bins threads for small batches: 512 (8 pairs: 35.5 -> 33.1 us against 1 024 — the passes run on
 // <= 512 list positions, so waves 8-15 only added issue contention; level 0's key sweep is slower, but the
@@ -4200,16 +2988,6 @@ hipError_t prepare_octree(const Geo& g, int maxcell) {
     }
     if (no <= 160 * 1024) e = raise_lds((const void*)k_octree, (int)no);
     return e;
-}
-
-hipError_t launch_resize_cascade(const Geo& g, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
-                                 const ResizeY* yt, const int16_t* strips, int n_strips, int off_b, int off_x,
-                                 int lds_bytes, int n_images, hipStream_t s, int* zero_word, long long* prof) {
-    if (g.nlevels < 2 || n_images <= 0) return hipSuccess;
-    if (lds_bytes > lds_limit((const void*)k_resize_cascade)) return hipErrorInvalidConfiguration;  // prepare_resize_cascade was not run
-    hipLaunchKernelGGL(k_resize_cascade, dim3(n_strips, n_images), dim3(kCasNT), (size_t)lds_bytes, s, g, in, in_pitch, ws,
-                       xt, yt, strips, off_b, off_x, zero_word, prof);
-    return hipGetLastError();
 }
 
 hipError_t launch_octree(const Geo& g, const CellGeo* cells, const int* cell_count, const uint32_t* slots,

@@ -374,22 +374,12 @@ __global__ __launch_bounds__(kGateThreads) void k_bow_gate(
 struct BowScratch {
     DevBuf<int32_t> d_qw, d_common, d_first;
     DevBuf<double> d_qv, d_score;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_ms = 0.f;
-    ~BowScratch() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    void init() {
-        if (!stream) HIPCK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : ev)
-            if (!e) HIPCK(hipEventCreate(&e));
-    }
+    TimedStream t;
+    ~BowScratch() { t.destroy(); }
     // query upload, one launch over n_slots device-resident vectors, results to host buffers; synchronous
     void run(const int32_t* q_word, const double* q_weight, int32_t nq, const KfdbSlot* d_slot, const int32_t* d_word,
              const double* d_weight, int64_t n_slots, int32_t* common, int32_t* first, double* score) {
+        hipStream_t stream = t.get();
         d_qw.ensure(nq);
         d_qv.ensure(nq);
         d_common.ensure(n_slots);
@@ -401,7 +391,7 @@ struct BowScratch {
         }
         const int64_t want = (n_slots + kBowWaves - 1) / kBowWaves;
         const unsigned blocks = (unsigned)std::min<int64_t>(want, kBowMaxBlocks);
-        HIPCK(hipEventRecord(ev[0], stream));
+        t.begin(stream);
         if (nq <= kBowLdsWords)
             hipLaunchKernelGGL(k_bow_score<true>, dim3(blocks), dim3(64 * kBowWaves), (size_t)nq * sizeof(int32_t),
                                stream, d_qw.p, d_qv.p, nq, d_slot, d_word, d_weight, n_slots, d_common.p, d_first.p,
@@ -410,12 +400,12 @@ struct BowScratch {
             hipLaunchKernelGGL(k_bow_score<false>, dim3(blocks), dim3(64 * kBowWaves), 0, stream, d_qw.p, d_qv.p, nq,
                                d_slot, d_word, d_weight, n_slots, d_common.p, d_first.p, d_score.p);
         HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(ev[1], stream));
+        t.end(stream);
         HIPCK(hipMemcpyAsync(common, d_common.p, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         HIPCK(hipMemcpyAsync(first, d_first.p, n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         HIPCK(hipMemcpyAsync(score, d_score.p, n_slots * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
-        HIPCK(hipEventElapsedTime(&last_ms, ev[0], ev[1]));
+        t.last_ms = t.elapsed_ms();
     }
 };
 
@@ -430,13 +420,9 @@ struct ManyScratch {
     DevBuf<double> d_score;
     DevBuf<char> d_up, d_down;
     HostBuf<char> h_up, h_down;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    TimedStream t;  // its events only: the calls run on the handle's stream
     int64_t limit = kManyScratchDefault;
-    float last_ms = 0.f;
-    ~ManyScratch() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    ~ManyScratch() { t.destroy(); }
 };
 
 }  // namespace orbfe
@@ -512,7 +498,7 @@ void regrow(orbfe_kfdb& d, int64_t need_words, int64_t need_slots) {
 
 // Bring the device copy up to date: only the arena tail and the changed slot range travel.
 void sync_device(orbfe_kfdb& d) {
-    d.sc.init();
+    d.sc.t.get();
     if ((size_t)d.word_cap > d.d_word.n || !d.d_word.p) {  // first use, or the arena regrew
         d.d_word.ensure(d.word_cap);
         d.d_weight.ensure(d.word_cap);
@@ -527,16 +513,16 @@ void sync_device(orbfe_kfdb& d) {
     if (nw > d.up_words) {
         const size_t k = (size_t)(nw - d.up_words);
         HIPCK(hipMemcpyAsync(d.d_word.p + d.up_words, &d.word[d.up_words], k * sizeof(int32_t), hipMemcpyHostToDevice,
-                             d.sc.stream));
+                             d.sc.t.stream));
         HIPCK(hipMemcpyAsync(d.d_weight.p + d.up_words, &d.weight[d.up_words], k * sizeof(double),
-                             hipMemcpyHostToDevice, d.sc.stream));
+                             hipMemcpyHostToDevice, d.sc.t.stream));
     }
     const int64_t hi = std::min<int64_t>(d.dirty_hi, (int64_t)d.slot.size());
     if (hi > d.dirty_lo)
         HIPCK(hipMemcpyAsync(d.d_slot.p + d.dirty_lo, &d.slot[d.dirty_lo], (size_t)(hi - d.dirty_lo) * sizeof(KfdbSlot),
-                             hipMemcpyHostToDevice, d.sc.stream));
+                             hipMemcpyHostToDevice, d.sc.t.stream));
     // the host vectors must not move before the copies have read them
-    HIPCK(hipStreamSynchronize(d.sc.stream));
+    HIPCK(hipStreamSynchronize(d.sc.t.stream));
     d.up_words = nw;
     d.dirty_lo = d.dirty_hi = 0;
 }
@@ -574,8 +560,6 @@ struct HostQueries {
     int64_t total;
 };
 
-inline size_t pad8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
-
 // Everything that can be refused, before any device call.  Returns false when the call is answered here: no
 // query, or an empty database (zeros).
 bool check_many(orbfe_kfdb& d, const ManyCall& a, const char* what) {
@@ -602,7 +586,7 @@ bool check_many(orbfe_kfdb& d, const ManyCall& a, const char* what) {
     }
     if (a.n_query > 0 && (o->common || o->first || o->score) && a.dense_stride < ns)
         throw Error(ORBFE_ECAPACITY, w + ": dense rows are shorter than the slot table");
-    d.many.last_ms = 0.f;
+    d.many.t.last_ms = 0.f;
     if (a.n_query == 0) return false;
     if (ns == 0) {
         std::memset(o->n_sharing, 0, (size_t)a.n_query * sizeof(int32_t));
@@ -622,16 +606,14 @@ void run_many(orbfe_kfdb& d, const HostQueries* hq, BowQueries dq, const ManyCal
     ManyScratch& m = d.many;
     const int64_t ns = (int64_t)d.slot.size();
     const size_t nq = (size_t)a.n_query, cap = (size_t)a.hit_cap;
-    for (hipEvent_t& e : m.ev)
-        if (!e) HIPCK(hipEventCreate(&e));
 
     // one upload: weights | q_off | excl_off | words | excl_slot
     const size_t n_ex = a.excl_off ? (size_t)a.excl_off[nq] : 0;
-    const size_t b_wt = hq ? pad8((size_t)hq->total * sizeof(double)) : 0;
+    const size_t b_wt = hq ? pad_to((size_t)hq->total * sizeof(double), 8) : 0;
     const size_t b_qo = hq ? (nq + 1) * sizeof(int64_t) : 0;
     const size_t b_eo = a.excl_off ? (nq + 1) * sizeof(int64_t) : 0;
-    const size_t b_wd = hq ? pad8((size_t)hq->total * sizeof(int32_t)) : 0;
-    const size_t b_es = pad8(n_ex * sizeof(int32_t));
+    const size_t b_wd = hq ? pad_to((size_t)hq->total * sizeof(int32_t), 8) : 0;
+    const size_t b_es = pad_to(n_ex * sizeof(int32_t), 8);
     const size_t o_qo = b_wt, o_eo = o_qo + b_qo, o_wd = o_eo + b_eo, o_es = o_wd + b_wd, up = o_es + b_es;
     if (up) {
         m.h_up.ensure(up);
@@ -676,7 +658,7 @@ void run_many(orbfe_kfdb& d, const HostQueries* hq, BowQueries dq, const ManyCal
         const int tiles = (n + kBowTile - 1) / kBowTile;
         const int64_t want = (ns + kBowManyWaves - 1) / kBowManyWaves;
         const unsigned gx = (unsigned)std::min<int64_t>(want, std::max(1, kBowMaxBlocks / tiles));
-        HIPCK(hipEventRecord(m.ev[0], stream));
+        m.t.begin(stream);
         hipLaunchKernelGGL(k_bow_score_many, dim3(gx, tiles), dim3(64 * kBowManyWaves),
                            (size_t)lds_words * sizeof(int32_t), stream, dq, q0, n, lds_words, d.d_slot.p, d.d_word.p,
                            d.d_weight.p, ns, m.d_common.p, m.d_first.p, m.d_score.p);
@@ -685,7 +667,7 @@ void run_many(orbfe_kfdb& d, const HostQueries* hq, BowQueries dq, const ManyCal
                            d.d_slot.p, ns, q0, d_eo, d_es, a.gate_ratio, a.hit_cap, d_nsh, d_max, d_nh, d_hslot,
                            d_hcommon, d_hfirst, d_hscore);
         HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(m.ev[1], stream));
+        m.t.end(stream);
         const auto rows_out = [&](void* dst, const void* src, size_t elem) {
             if (!dst) return;
             char* to = (char*)dst + (size_t)q0 * a.dense_stride * elem;
@@ -703,11 +685,9 @@ void run_many(orbfe_kfdb& d, const HostQueries* hq, BowQueries dq, const ManyCal
         if (q0 + n == a.n_query)
             HIPCK(hipMemcpyAsync(m.h_down.p, m.d_down.p, down, hipMemcpyDeviceToHost, stream));
         HIPCK(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        HIPCK(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
-        total_ms += ms;
+        total_ms += m.t.elapsed_ms();
     }
-    m.last_ms = total_ms;
+    m.t.last_ms = total_ms;
 
     const int32_t* h_int = (const int32_t*)(m.h_down.p + o_int);
     std::memcpy(o.n_sharing, h_int, nq * sizeof(int32_t));
@@ -814,7 +794,7 @@ int orbfe_kfdb_query(orbfe_kfdb_handle h, const int32_t* q_word, const double* q
         orbfe_kfdb& d = *h;
         const int64_t ns = (int64_t)d.slot.size();
         if (cap < ns) throw Error(ORBFE_ECAPACITY, "result arrays are shorter than the slot table");
-        d.sc.last_ms = 0.f;
+        d.sc.t.last_ms = 0.f;
         if (ns == 0) return;
         if (!common || !first || !score) throw Error(ORBFE_EINVAL, "null result array");
         sync_device(d);
@@ -841,18 +821,18 @@ int orbfe_bow_score(const int32_t* q_word, const double* q_weight, int32_t nq, c
             p.slot[v] = KfdbSlot{off[v], (int32_t)len, 1};
         }
         const int64_t total = off[n_vec];
-        p.sc.init();
+        p.sc.t.get();
         p.d_word.ensure(total);
         p.d_weight.ensure(total);
         p.d_slot.ensure(n_vec);
         if (total) {
             HIPCK(hipMemcpyAsync(p.d_word.p, word, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 p.sc.stream));
+                                 p.sc.t.stream));
             HIPCK(hipMemcpyAsync(p.d_weight.p, weight, (size_t)total * sizeof(double), hipMemcpyHostToDevice,
-                                 p.sc.stream));
+                                 p.sc.t.stream));
         }
         HIPCK(hipMemcpyAsync(p.d_slot.p, p.slot.data(), (size_t)n_vec * sizeof(KfdbSlot), hipMemcpyHostToDevice,
-                             p.sc.stream));
+                             p.sc.t.stream));
         p.sc.run(q_word, q_weight, nq, p.d_slot.p, p.d_word.p, p.d_weight.p, n_vec, common, first, score);
     });
 }
@@ -893,7 +873,7 @@ int orbfe_kfdb_query_many(orbfe_kfdb_handle h, const int64_t* q_off, const int32
         }
         sync_device(*h);
         HostQueries hq{q_off, q_word, q_weight, total};
-        run_many(*h, &hq, BowQueries{}, a, lds_words, h->sc.stream);
+        run_many(*h, &hq, BowQueries{}, a, lds_words, h->sc.t.stream);
     });
 }
 
@@ -929,7 +909,7 @@ int orbfe_kfdb_many_last_ms(orbfe_kfdb_handle h, float* ms) {
     return guarded([&] {
         if (!h || !ms) throw Error(ORBFE_EINVAL, "null argument");
         std::lock_guard<std::mutex> lk(h->mu);
-        *ms = h->many.last_ms;
+        *ms = h->many.t.last_ms;
     });
 }
 
@@ -937,7 +917,7 @@ int orbfe_kfdb_last_ms(orbfe_kfdb_handle h, float* ms) {
     return guarded([&] {
         if (!h || !ms) throw Error(ORBFE_EINVAL, "null argument");
         std::lock_guard<std::mutex> lk(h->mu);
-        *ms = h->sc.last_ms;
+        *ms = h->sc.t.last_ms;
     });
 }
 

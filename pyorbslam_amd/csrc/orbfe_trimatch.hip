@@ -33,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "orbfe_device.h"
 #include "orbfe_host_util.h"
 
 using namespace orbfe;
@@ -72,21 +73,6 @@ struct TmOut {
     int8_t* bin12;
     int32_t *hist, *n_raw, *status;
 };
-
-__device__ __forceinline__ unsigned tm_dist(const uint4& a, const uint4& b, const uint4& qa, const uint4& qb) {
-    return __popc(a.x ^ qa.x) + __popc(a.y ^ qa.y) + __popc(a.z ^ qa.z) + __popc(a.w ^ qa.w) + __popc(b.x ^ qb.x) +
-           __popc(b.y ^ qb.y) + __popc(b.z ^ qb.z) + __popc(b.w ^ qb.w);
-}
-
-// lane j's value, j wave-uniform
-__device__ __forceinline__ unsigned tm_lane(unsigned v, int j) {
-    return (unsigned)__builtin_amdgcn_readlane((int)v, j);
-}
-__device__ __forceinline__ double tm_lane(double v, int j) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = tm_lane((unsigned)b, j), hi = tm_lane((unsigned)(b >> 32), j);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 __device__ __forceinline__ unsigned tm_min(unsigned m) {
 #pragma unroll
@@ -207,10 +193,10 @@ __global__ __launch_bounds__(64 * kTmWaves) void k_tri_match(TmFrames fr, TmPair
             }
             const int i1 = __builtin_amdgcn_readlane(my_i1, j);
             if (i1 < 0) continue;
-            const uint4 qa = make_uint4(tm_lane(ma.x, j), tm_lane(ma.y, j), tm_lane(ma.z, j), tm_lane(ma.w, j));
-            const uint4 qb = make_uint4(tm_lane(mb.x, j), tm_lane(mb.y, j), tm_lane(mb.z, j), tm_lane(mb.w, j));
+            const uint4 qa = make_uint4(lane_value(ma.x, j), lane_value(ma.y, j), lane_value(ma.z, j), lane_value(ma.w, j));
+            const uint4 qb = make_uint4(lane_value(mb.x, j), lane_value(mb.y, j), lane_value(mb.z, j), lane_value(mb.w, j));
             const bool mono1 = __builtin_amdgcn_readlane(my_mono1, j) != 0;
-            const double x1 = tm_lane(my_x1, j), y1 = tm_lane(my_y1, j);
+            const double x1 = lane_value(my_x1, j), y1 = lane_value(my_y1, j);
             // the epipolar line of i1 in frame 2 (check_dist_epipolar_line, ORBMatcher.py:699-704), once per i1
             const double a = x1 * F00 + y1 * F10 + F20;
             const double b = x1 * F01 + y1 * F11 + F21;
@@ -222,7 +208,7 @@ __global__ __launch_bounds__(64 * kTmWaves) void k_tri_match(TmFrames fr, TmPair
                 unsigned key = kTmNone;
                 if (c0 == 0) {
                     if (i2_0 >= 0 && !blk[i2_0]) {
-                        const unsigned d = tm_dist(ea, eb, qa, qb);
+                        const unsigned d = hamming256(ea, eb, qa, qb);
                         if ((int)d <= th &&
                             tm_gates(mono1 && mono2_0, ex, ey, a, b, c, den, x2_0, y2_0, tex_0, tepi_0, marginal))
                             key = (d << 16) | (0xFFFFu - (unsigned)pos);
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(64 * kTmWaves) void k_tri_match(TmFrames fr, TmPair
                 } else if (pos < len2) {
                     const int i2 = idx2[a2 + pos];
                     if (!blk[i2]) {
-                        const unsigned d = tm_dist(desc2[2 * i2], desc2[2 * i2 + 1], qa, qb);
+                        const unsigned d = hamming256(desc2[2 * i2], desc2[2 * i2 + 1], qa, qb);
                         if ((int)d <= th) {
                             const int o = oct2[i2];
                             if (tm_gates(mono1 && !(fl2[i2] & ORBFE_TRI_STEREO), ex, ey, a, b, c, den, xy2[2 * i2],
@@ -296,23 +282,14 @@ struct TriMatcher {
     DevBuf<int8_t> d_bin;
     std::vector<int32_t> h_match;  // host staging of match12
     std::vector<int8_t> h_bin;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_ms = 0.f;
+    TimedStream t;
 };
 TriMatcher& tri_matcher() {
     static TriMatcher* m = new TriMatcher;
     return *m;
 }
 
-std::string at_frame(int32_t f, const char* what) { return "frame " + std::to_string(f) + ": " + what; }
 std::string at_pair(int32_t p, const char* what) { return "pair " + std::to_string(p) + ": " + what; }
-
-bool all_finite(const double* v, int64_t n) {
-    for (int64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
 
 // The reference's walk over two ascending node lists (ORBMatcher.py:604-677): the visited (run 1, run 2) pairs are
 // appended to vis; false when the discard of the smaller side finds its list exhausted (StopIteration escapes).
@@ -373,33 +350,11 @@ int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy,
                 const int32_t o = octave[off[f] + i];
                 if (o < 0 || o >= nl) throw Error(ORBFE_EINVAL, at_frame(f, "an octave is outside the level table"));
             }
-            seen.assign((size_t)n, 0);
-            int64_t prev_end = 0;
-            for (int64_t r = 0; r < nn; ++r) {
-                const int64_t at = fv_off[f] + r;
-                if (r > 0 && fv_node[at] <= fv_node[at - 1])
-                    throw Error(ORBFE_EINVAL, at_frame(f, "feature vector nodes must be strictly ascending"));
-                const int64_t end = fv_end[at];
-                if (end < prev_end) throw Error(ORBFE_EINVAL, at_frame(f, "feature vector run ends must not decrease"));
-                if (end > n) throw Error(ORBFE_EINVAL, at_frame(f, "a feature vector run ends past the index count"));
-                if (end > prev_end && !fv_idx) throw Error(ORBFE_EINVAL, "null argument");
-                for (int64_t k = prev_end; k < end; ++k) {
-                    const int32_t i = fv_idx[off[f] + k];
-                    if (i < 0 || i >= n) throw Error(ORBFE_EINVAL, at_frame(f, "a feature index is out of range"));
-                    if (seen[i]) throw Error(ORBFE_EINVAL, at_frame(f, "a feature index appears twice"));
-                    seen[i] = 1;
-                }
-                prev_end = end;
-            }
+            check_frame_runs(f, off, fv_off, fv_node, fv_end, fv_idx, seen);
         }
         int64_t longest = 0;
         for (int32_t p = 0; p < n_pairs; ++p) {
-            for (int s = 0; s < 2; ++s) {
-                const int32_t f = pairs[2 * p + s];
-                if (f < 0 || f >= n_frames)
-                    throw Error(ORBFE_EINVAL, "pair " + std::to_string(p) + " names frame " + std::to_string(f) +
-                                                  ", which does not exist");
-            }
+            check_pair_frames(pairs, p, n_frames);
             longest = std::max(longest, off[pairs[2 * p] + 1] - off[pairs[2 * p]]);
             if (!all_finite(F12 + 9 * (int64_t)p, 9)) throw Error(ORBFE_EINVAL, at_pair(p, "F12 is not finite"));
             if (!all_finite(epipole + 2 * (int64_t)p, 2))
@@ -424,10 +379,7 @@ int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy,
         const size_t nv = vis.size() / 2;
         TriMatcher& m = tri_matcher();
         std::lock_guard<std::mutex> lk(m.mu);
-        if (!m.stream) HIPCK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : m.ev)
-            if (!e) HIPCK(hipEventCreate(&e));
-        hipStream_t s = m.stream;
+        hipStream_t s = m.t.get();
         const size_t nf1 = (size_t)n_frames + 1;
         m.d_desc.ensure((size_t)n * 32);
         m.d_flags.ensure(n);
@@ -492,11 +444,11 @@ int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy,
         d.n_raw = d.hist + 32 * np;
         d.status = d.n_raw + np;
         d.bin12 = m.d_bin.p;
-        HIPCK(hipEventRecord(m.ev[0], s));
+        m.t.begin(s);
         hipLaunchKernelGGL(k_tri_match, dim3((unsigned)n_pairs), dim3(64 * kTmWaves), 0, s, fr, pr, (int)th,
                            (int)(only_stereo != 0), d);
         HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(m.ev[1], s));
+        m.t.end(s);
         // the blocks come back whole into staging; only the entries the kernel wrote, [0, n1) of each pair's block,
         // reach the caller's arrays
         m.h_match.resize(np * os);
@@ -509,7 +461,7 @@ int orbfe_tri_match(const uint8_t* desc32, const float* angle, const double* xy,
         HIPCK(hipMemcpyAsync(out->n_raw, d.n_raw, np * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCK(hipMemcpyAsync(out->status, d.status, np * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
-        HIPCK(hipEventElapsedTime(&m.last_ms, m.ev[0], m.ev[1]));
+        m.t.last_ms = m.t.elapsed_ms();
         for (size_t p = 0; p < np; ++p) {
             const size_t l1 = (size_t)(off[pairs[2 * p] + 1] - off[pairs[2 * p]]);
             if (l1) {
@@ -525,7 +477,7 @@ int orbfe_tri_match_last_ms(float* ms) {
         if (!ms) throw Error(ORBFE_EINVAL, "null argument");
         TriMatcher& m = tri_matcher();
         std::lock_guard<std::mutex> lk(m.mu);
-        *ms = m.last_ms;
+        *ms = m.t.last_ms;
     });
 }
 

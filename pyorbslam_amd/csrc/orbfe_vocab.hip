@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "orbfe_device.h"
 #include "orbfe_host_util.h"
 
 using namespace orbfe;
@@ -46,25 +47,19 @@ struct orbfe_vocab {
     DevBuf<uint8_t> d_q;
     DevBuf<int32_t> d_word, d_node;
     DevBuf<double> d_w;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_ms = 0.f;
+    TimedStream t;  // orbfe_vocab_transform
     // orbfe_vocab_bow: frame offsets, the i32 outputs (4 per-entry arrays, 3 per-frame arrays) and the weights
     DevBuf<int64_t> d_off;
     DevBuf<int32_t> d_bow_i;
     DevBuf<double> d_bow_w;
-    hipEvent_t ev_bow[2] = {nullptr, nullptr};
-    float bow_ms = 0.f;
+    TimedStream t_bow;  // orbfe_vocab_bow: its events only, on t's stream
     // transform callers share one vocabulary across threads (Frame.compute_BoW on the tracking thread,
     // KeyFrame.compute_bow on the mapping thread: Frame.py:125, KeyFrame.py:119): the scratch buffers,
     // the stream and the events above are guarded by this mutex
     std::mutex mu;
     ~orbfe_vocab() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_bow)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
+        t_bow.destroy();
+        t.destroy();
     }
 };
 
@@ -93,8 +88,7 @@ __device__ __forceinline__ void descend_one(const uint8_t* __restrict__ qi, int 
                 const uint4 a = slot_desc[2 * (start + j)];
                 const uint4 b = slot_desc[2 * (start + j) + 1];
                 const int4 inf = slot_info[start + j];
-                unsigned d = __popc(a.x ^ qa.x) + __popc(a.y ^ qa.y) + __popc(a.z ^ qa.z) + __popc(a.w ^ qa.w) +
-                             __popc(b.x ^ qb.x) + __popc(b.y ^ qb.y) + __popc(b.z ^ qb.z) + __popc(b.w ^ qb.w);
+                const unsigned d = hamming256(a, b, qa, qb);
                 const unsigned key = (d << 16) | (unsigned)j;
                 if (key < best) {
                     best = key;
@@ -464,11 +458,7 @@ void finish(orbfe_vocab& v) {
 
 void upload(orbfe_vocab& v) {
     if (v.uploaded) return;
-    if (!v.stream) HIPCK(hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : v.ev)
-        if (!e) HIPCK(hipEventCreate(&e));
-    for (hipEvent_t& e : v.ev_bow)
-        if (!e) HIPCK(hipEventCreate(&e));
+    v.t.get();
     const size_t ns = v.slot_info.size();
     std::vector<uint8_t> sd(std::max<size_t>(ns, 1) * 32, 0);
     for (size_t s = 0; s < ns; ++s) std::memcpy(&sd[s * 32], &v.desc[(size_t)v.slot_info[s].x * 32], 32);
@@ -714,15 +704,15 @@ int orbfe_vocab_transform(orbfe_vocab_handle v, const uint8_t* desc32, int64_t n
         v->d_word.ensure(n);
         v->d_node.ensure(n);
         v->d_w.ensure(n);
-        HIPCK(hipMemcpyAsync(v->d_q.p, desc32, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
-        HIPCK(hipEventRecord(v->ev[0], v->stream));
-        launch_descend(*v, v->d_q.p, n, nid_level, v->d_word.p, v->d_node.p, v->d_w.p, v->stream);
-        HIPCK(hipEventRecord(v->ev[1], v->stream));
-        HIPCK(hipMemcpyAsync(word_id, v->d_word.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-        HIPCK(hipMemcpyAsync(node_id, v->d_node.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-        HIPCK(hipMemcpyAsync(weight, v->d_w.p, n * sizeof(double), hipMemcpyDeviceToHost, v->stream));
-        HIPCK(hipStreamSynchronize(v->stream));
-        HIPCK(hipEventElapsedTime(&v->last_ms, v->ev[0], v->ev[1]));
+        HIPCK(hipMemcpyAsync(v->d_q.p, desc32, (size_t)n * 32, hipMemcpyHostToDevice, v->t.stream));
+        v->t.begin(v->t.stream);
+        launch_descend(*v, v->d_q.p, n, nid_level, v->d_word.p, v->d_node.p, v->d_w.p, v->t.stream);
+        v->t.end(v->t.stream);
+        HIPCK(hipMemcpyAsync(word_id, v->d_word.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v->t.stream));
+        HIPCK(hipMemcpyAsync(node_id, v->d_node.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, v->t.stream));
+        HIPCK(hipMemcpyAsync(weight, v->d_w.p, n * sizeof(double), hipMemcpyDeviceToHost, v->t.stream));
+        HIPCK(hipStreamSynchronize(v->t.stream));
+        v->t.last_ms = v->t.elapsed_ms();
     });
 }
 
@@ -827,14 +817,14 @@ int orbfe_vocab_bow(orbfe_vocab_handle v, const uint8_t* desc32, const int64_t* 
         d.n_nodes = d.n_words + n_frames;
         d.n_kept = d.n_nodes + n_frames;
         d.bow_weight = v->d_bow_w.p;
-        hipStream_t s = v->stream;
+        hipStream_t s = v->t.stream;
         HIPCK(hipMemcpyAsync(v->d_q.p, desc32, (size_t)n * 32, hipMemcpyHostToDevice, s));
         HIPCK(hipMemcpyAsync(v->d_off.p, off, ((size_t)n_frames + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        HIPCK(hipEventRecord(v->ev_bow[0], s));
+        v->t_bow.begin(s);
         launch_descend(*v, v->d_q.p, n, nid_level, v->d_word.p, v->d_node.p, v->d_w.p, s);
         launch_assemble(BowFrames{v->d_off.p, nullptr, 0, 0, 0}, n_frames, longest, v->d_word.p, v->d_node.p, v->d_w.p,
                         d, s);
-        HIPCK(hipEventRecord(v->ev_bow[1], s));
+        v->t_bow.end(s);
         const size_t ni = (size_t)n * sizeof(int32_t), nf = (size_t)n_frames * sizeof(int32_t);
         HIPCK(hipMemcpyAsync(out->bow_word, d.bow_word, ni, hipMemcpyDeviceToHost, s));
         HIPCK(hipMemcpyAsync(out->bow_weight, d.bow_weight, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -845,7 +835,7 @@ int orbfe_vocab_bow(orbfe_vocab_handle v, const uint8_t* desc32, const int64_t* 
         HIPCK(hipMemcpyAsync(out->n_nodes, d.n_nodes, nf, hipMemcpyDeviceToHost, s));
         HIPCK(hipMemcpyAsync(out->n_kept, d.n_kept, nf, hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
-        HIPCK(hipEventElapsedTime(&v->bow_ms, v->ev_bow[0], v->ev_bow[1]));
+        v->t_bow.last_ms = v->t_bow.elapsed_ms();
     });
 }
 
@@ -853,7 +843,7 @@ int orbfe_vocab_bow_last_ms(orbfe_vocab_handle v, float* ms) {
     return guarded([&] {
         if (!v || !ms) throw Error(ORBFE_EINVAL, "null argument");
         std::lock_guard<std::mutex> lk(v->mu);
-        *ms = v->bow_ms;
+        *ms = v->t_bow.last_ms;
     });
 }
 
@@ -861,7 +851,7 @@ int orbfe_vocab_last_ms(orbfe_vocab_handle v, float* ms) {
     return guarded([&] {
         if (!v || !ms) throw Error(ORBFE_EINVAL, "null argument");
         std::lock_guard<std::mutex> lk(v->mu);
-        *ms = v->last_ms;
+        *ms = v->t.last_ms;
     });
 }
 

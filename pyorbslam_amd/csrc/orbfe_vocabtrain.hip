@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "orbfe_device.h"
 #include "orbfe_host_util.h"
 
 using namespace orbfe;
@@ -36,11 +37,6 @@ struct TrainSeg {
 struct TrainChunk {
     int32_t seg, begin, end, pad;
 };
-
-__device__ __forceinline__ int ham256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // Sum over the workgroup; every thread gets it.  wsum: kTrainThreads / 64 words of LDS, free again on return.
 __device__ __forceinline__ unsigned block_sum(unsigned v, unsigned* wsum, int tid) {
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_seed_dist(const TrainCh
     for (int o = tid; o < c.end - c.begin; o += kTrainThreads) {  // by offset: pos + 256 may pass 2^31
         const int pos = c.begin + o;
         const int64_t i = order[pos];
-        unsigned d = (unsigned)ham256(D[i * 2], D[i * 2 + 1], c0, c1);
+        unsigned d = hamming256(D[i * 2], D[i * 2 + 1], c0, c1);
         if (j > 0) d = min(d, md[pos]);
         md[pos] = d;
         sum += d;
@@ -169,9 +165,9 @@ __global__ __launch_bounds__(kTrainThreads) void k_train_assign(const TrainChunk
         const int pos = c.begin + o;
         const int64_t i = order[pos];
         const uint4 q0 = D[i * 2], q1 = D[i * 2 + 1];
-        int best = 0, bd = ham256(q0, q1, sc[0], sc[1]);
+        int best = 0, bd = (int)hamming256(q0, q1, sc[0], sc[1]);
         for (int cc = 1; cc < nc; ++cc) {
-            const int d = ham256(q0, q1, sc[2 * cc], sc[2 * cc + 1]);
+            const int d = (int)hamming256(q0, q1, sc[2 * cc], sc[2 * cc + 1]);
             if (d < bd) bd = d, best = cc;
         }
         if (assign[pos] != (uint8_t)best) {

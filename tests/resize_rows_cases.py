@@ -1,5 +1,5 @@
 """Geometries of tests/test_gpu_resize_rows.py and a restatement, in Python, of the rules by which the host
-shapes a k_resize_rows launch (launch_resize in orbfe_kernels.hip, the band and y-table rules of orbfe_host.hip,
+shapes a k_resize_rows launch (launch_resize in orbfe_resize.hip, the band and y-table rules of orbfe_host.hip,
 the end of the vertical pass's vector span).  tests/test_resize_rows_cases_cpu.py uses the restatement to show
 that the geometries reach the kernel's paths they are chosen for."""
 from __future__ import annotations

@@ -82,6 +82,26 @@ def test_gpu_push_carries_no_dev_variant_libraries():
     assert "./bench.py" in names and "./tests/golden/" in names
 
 
+def test_makefile_lists_every_source_and_header():
+    """orbfe_build_id() hashes $(SRC) $(CSRC) $(HDR), and $(OBJ) is derived from SRC and CSRC: a file of the
+    product source that the Makefile does not list changes the library without changing its id, or is not
+    built at all.  Every *.hip under pyorbslam_amd/csrc is in SRC, every *.cpp but the CPython extension
+    (orbfe_pyhost.cpp, a target of its own) in CSRC, every *.h and *.inc plus include/orbfe.h in HDR; and
+    nothing listed is missing."""
+    text = (ROOT / "Makefile").read_text().replace("\\\n", " ")
+    listed = {}
+    for var in ("SRC", "CSRC", "HDR"):
+        m = re.search(rf"^{var} := (.*)$", text, re.M)
+        assert m, f"Makefile sets no {var}"
+        listed[var] = sorted(m.group(1).split())
+        assert len(set(listed[var])) == len(listed[var]), f"{var} lists a file twice"
+    csrc = ROOT / "pyorbslam_amd" / "csrc"
+    rel = lambda paths: sorted(str(p.relative_to(ROOT)) for p in paths)
+    assert listed["SRC"] == rel(csrc.glob("*.hip"))
+    assert listed["CSRC"] == rel(p for p in csrc.glob("*.cpp") if p.name != "orbfe_pyhost.cpp")
+    assert listed["HDR"] == rel(list(csrc.glob("*.h")) + list(csrc.glob("*.inc")) + [ROOT / "include" / "orbfe.h"])
+
+
 def test_buffer_resources_built_only_by_the_helpers():
     """Every buffer resource of the kernels is built by uniform_rsrc / bounded_rsrc / aligned_rsrc, which pass the
     address halves through uint32_t: __builtin_amdgcn_readfirstlane returns int, and an ad-hoc construction that

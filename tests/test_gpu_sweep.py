@@ -133,7 +133,8 @@ def test_mixed_batch_in_every_launch_shape(hw, n_pairs):
     _check_batch(fe, mb, n_pairs, "batch")
     assert any((r.status == 1).any() for r in mb.pair_refs) and any((r.status == 2).any() for r in mb.pair_refs)
 
-    # which shapes the launchers' own rules picked for this batch (orbfe_kernels.hip): k_resize_rows,
+    # which shapes the launchers' own rules picked for this batch (the launch_* of orbfe_resize.hip,
+    # orbfe_detect.hip and orbfe_kernels.hip): k_resize_rows,
     # k_octree_bins<256> and k_stereo_bucket<256> from n_images >= kSmallBatchImages (32); detect_cpw: four cells
     # per wave from n_images * ceil(ncells / 4) >= 8 * 256 as well; orb_kpw: 8 keypoints per wave from
     # n_images * sum over levels of ceil(level kp_cap / 8) >= 16 * 256, which n_images * kp_cap / 8 implies

@@ -1,6 +1,6 @@
 """The packed level keys of round 6 ((x + y * w) | score << 24, orbfe_common.h kKeyXYBits) are decoded in the
 kernels as y = mul_hi(xy, mag) >> sh, x = xy - y * w with mag = ceil(2^(31 + s) / w), sh = s - 1,
-s = ceil(log2 w) (orbfe_host.hip key_divisor, orbfe_kernels.hip key_xy).  This pins that arithmetic on the
+s = ceil(log2 w) (orbfe_host.hip key_divisor, orbfe_device.h key_xy).  This pins that arithmetic on the
 CPU for every level width the library accepts (2 .. 32 767): exact floor division for the indices where the
 error term is largest (the last rows below 2^24) and at every row boundary of the first rows."""
 import numpy as np
