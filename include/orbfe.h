@@ -44,7 +44,8 @@ extern "C" {
                                * orbfe_kfdb_many_last_ms and orbfe_kfdb_many_out, and orbfe_scw_search,
                                * orbfe_scw_search_last_ms and orbfe_scw_out, and orbfe_sim3_search,
                                * orbfe_sim3_search_last_ms and orbfe_sim3_out, and orbfe_fkf_search,
-                               * orbfe_fkf_search_last_ms and orbfe_fkf_out, and orbfe_debug_detect_lanes */
+                               * orbfe_fkf_search_last_ms and orbfe_fkf_out, and orbfe_debug_detect_lanes, and
+                               * orbfe_local_search, orbfe_local_search_last_ms and orbfe_local_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -898,6 +899,68 @@ int orbfe_fkf_search(const double* kf_f64, const int32_t* kf_i32, const int64_t*
                      double th, double eps, const orbfe_fkf_out* out);
 /* Kernel time of the last orbfe_fkf_search (ms, HIP events), for measurement. */
 int orbfe_fkf_search_last_ms(float* ms);
+
+/* ---- tracking's local-map search (Tracking.search_local_points, Tracking.py:439-468: Frame.is_in_frustum,
+ *      Frame.py:328-371, then ORBMatcher.search_by_projection_f_p, ORBMatcher.py:215-283) ----
+ *
+ * k_local_search, one launch for n_srch searches.  A search is a target frame, a limit of the viewing cosine and a
+ * list of map points of its own (the local map, after the caller's prefilter).  For every item it decides what
+ * is_in_frustum decides (in view or not, the predicted level) and, for an item in view, finds the best and the second
+ * best candidate of search_by_projection_f_p.  The TH_HIGH test, the ratio test between the two (with the octaves of
+ * best_idx and second_idx), the assignment into the frame's map point slots and the attributes is_in_frustum writes
+ * stay with the caller, in the reference's order; because an assignment by a point with observations takes a feature
+ * away from the items after it, the caller redoes an item whose best or second feature was taken meanwhile.
+ * The target arrays are orbfe_fkf_search's, `blocked` included, plus u_right (one double per feature, concatenated at
+ * `off`; <= 0: the feature has no stereo gate, the reference tests mvuRight[idx] > 0), and slot [4] of a block, bf, is
+ * read.  The point table is orbfe_fuse_search's with the normal in slots [3..5], which is read.  The searches are
+ * orbfe_fkf_search's plus srch_limit[s], the viewing cosine's limit (0.5 in Tracking).
+ * Per item, in IEEE double in this operation order without contraction (sums of three from the left):
+ *   pc = Rcw p + tcw; pc.z < 0: not in view.  invz = 1 / pc.z; u = (fx * pc.x) * invz + cx, v likewise,
+ *   ur = u - bf * invz; mnMinX <= u <= mnMaxX and mnMinY <= v <= mnMaxY; PO = p - Ow, dist = sqrt(PO.PO) in [min, max]
+ *   distance; view_cos = (PO.n) / dist, below srch_limit[s]: not in view; level = ceil(log(mfMaxDistance / dist) /
+ *   mfLogScaleFactor) clamped to [0, levels - 1].  The item is in view.
+ *   r0 = view_cos > 0.998 ? 2.5 : 4.0; r0 *= th only where th_on != 0 (the caller's th != 1.0; with th_on == 0 th is
+ *   not read); r = r0 * scale[level]; the cell window is orbfe_fkf_search's, truncated at both ends.
+ *   A candidate is an entry of the window's cells in orbfe_scw_search's visiting order whose blocked byte is 0, with
+ *   |x - u| < r and |y - v| < r, octave in [level - 1, level], and, where u_right[f] > 0, |ur - u_right[f]| <= r.
+ *   best is the candidate of the smallest key (Hamming distance, visiting position), second that of the second
+ *   smallest: what the reference's sequential update (dist < best shifts best into second, else dist < best2 sets
+ *   second) holds after the last candidate.
+ * Outputs at [i], i < srch_off[n_srch], flat over the items: in_view (0 / 1), level (-1 when not in view), best_idx,
+ * best_dist, second_idx, second_dist (-1 for none; all four -1 when not in view), status.  status gets
+ * ORBFE_FUSE_MARGINAL under orbfe_fkf_search's bounds scaled by eps (the sign of pc.z, an image bound, the minimum or
+ * maximum distance, the level quotient near an integer, a window bound near an integer of magnitude >= 1, a visited
+ * entry's |dx| or |dy| near r; a blocked entry marks nothing) and for: view_cos within its bound of srch_limit[s] or
+ * of 0.998 (the bound is 5 eps (sum of the dot product's term magnitudes) / dist + 8 eps |view_cos|, plus eps times
+ * the threshold); a candidate with u_right > 0 that passed the position and octave tests whose |ur - uR| lies within
+ * its bound of r (ur's bound is orbfe_fuse_search's); pc.z == 0 (the reference's NaN comparisons can let such a point
+ * through its bounds); an intermediate that is not finite.  The outputs of a marked item are this arithmetic's.  The
+ * limits are orbfe_fuse_search's.  A workgroup takes up to ORBFE_FUSE_CHUNK items of one search; an empty search
+ * launches nothing. */
+typedef struct orbfe_local_out {
+    uint8_t* in_view;     /* one per item */
+    int32_t* level;       /* one per item */
+    int32_t* best_idx;    /* one per item */
+    int32_t* best_dist;   /* one per item */
+    int32_t* second_idx;  /* one per item */
+    int32_t* second_dist; /* one per item */
+    uint8_t* status;      /* one per item */
+} orbfe_local_out;
+/* Host buffers, synchronous; the target arrays and their checks are orbfe_fkf_search's, with u_right required and
+ * finite where a frame has features and slot [4] of a block finite; the searches' checks are orbfe_fkf_search's, and
+ * ORBFE_EINVAL, before any device call, also for a srch_limit that is not finite and for any point scalar that is not
+ * finite (the normal included).  n_srch == 0 or srch_off[n_srch] == 0 launches nothing and succeeds.  Process-wide
+ * buffers, stream and events of its own: concurrent callers take turns, and none of them waits for a caller of the
+ * other four searches. */
+int orbfe_local_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                       const int32_t* octave, const double* u_right, const uint8_t* desc32, const uint8_t* blocked,
+                       const int64_t* cell_at, const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx,
+                       const int64_t* lvl_off, const double* scale, int32_t n_kf, const double* pt_f64,
+                       const uint8_t* pt_desc32, int64_t n_pts, const double* srch_limit, const int32_t* srch_kf,
+                       const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt, double th, int32_t th_on,
+                       double eps, const orbfe_local_out* out);
+/* Kernel time of the last orbfe_local_search (ms, HIP events), for measurement. */
+int orbfe_local_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

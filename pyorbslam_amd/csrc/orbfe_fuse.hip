@@ -3,7 +3,9 @@
 // Sim3 searches, ORBMatcher.fuse_kf_scw_mp (:395-480) and ORBMatcher.search_by_projection_ckf_scw_mp (:850-922), as
 // k_scw_search; and the two directions of ORBMatcher.search_by_sim3 (:713-848) for many keyframe pairs as
 // k_sim3_search; and relocalisation's ORBMatcher.search_by_projection_f_kf_f (:924-1008) into many frames as
-// k_fkf_search.  All four kernels are instantiations of one body, proj_search<kMode>.
+// k_fkf_search; and tracking's local-map search, Frame.is_in_frustum (Frame.py:328-371) followed by
+// ORBMatcher.search_by_projection_f_p (:215-283), as k_local_search.  All five kernels are instantiations of one body,
+// proj_search<kMode>.
 //
 // The reference projects each map point into a keyframe, gates it (depth sign, image bounds, scale-invariance
 // distances, viewing angle), predicts its pyramid level, searches the keyframe's grid in a window of radius
@@ -42,6 +44,15 @@
 //                  read.  Both ends of the cell window truncate toward zero (int()), so a bound in (-1, 1) is cell 0
 //                  and only the integers of magnitude >= 1 can flip one.  A candidate's octave lies in
 //                  [level - 1, level + 1]: three octaves, the others keep two.
+//
+//   k_local_search is k_fkf_search's Frame target, ragged launch and blocked byte with what tracking's search adds:
+//                  the depth gate pc.z < 0 (pc.z == 0 marks: the reference's NaN comparisons can let such a point
+//                  through); ur = u - bf / z as in k_fuse_search; the viewing gate on the cosine itself,
+//                  (PO . n) / dist < limit with one limit per search; the radius from the cosine (2.5 above 0.998,
+//                  else 4, times th only where the caller's th != 1, times scale[level]); two octaves; a stereo gate
+//                  per candidate (a feature whose right coordinate is > 0 is left out when |ur - uR| > r); and the
+//                  second smallest key besides the smallest.  It also gives what is_in_frustum decides: in_view and
+//                  the level, which stand whatever becomes of the window.
 //
 // The depth gate: fuse_pkf_mp and fuse_kf_scw_mp skip z < 0, the ckf search z <= 0.  At z == 0 the first two run on to
 // 1 / 0, u and v become inf or NaN and fail the image test, so all three skip the point and one code path serves them.
@@ -105,19 +116,23 @@ struct PsPts {
 struct PsOut {
     int32_t *best_idx, *best_dist;
     uint8_t* status;
-    int64_t stride;  // k_sim3_search, k_fkf_search: not read, the outputs are flat over the items
+    int64_t stride;  // k_sim3_search, k_fkf_search, k_local_search: not read, the outputs are flat over the items
+    // k_local_search only
+    int32_t *second_idx, *second_dist, *level;
+    uint8_t* in_view;
 };
 
 // k_sim3_search and k_fkf_search: the searches, their items and the launch's chunk table
 struct PsSim3 {
-    const double* f64;       // kPsSim3F64 per search; k_fkf_search: null, a search has no scalars of its own
+    const double* f64;       // kPsSim3F64 per search; k_fkf_search: null, a search has no scalars of its own;
+                             // k_local_search: one per search, the viewing cosine's limit
     const int32_t* kf;       // target keyframe per search
     const int64_t* off;      // search s owns items [off[s], off[s + 1])
     const int32_t* item_pt;  // point table row per item
     const int64_t* chunk;    // (search, first item) per workgroup
 };
 
-enum PsMode { kPsFuse, kPsScw, kPsSim3, kPsFkf };
+enum PsMode { kPsFuse, kPsScw, kPsSim3, kPsFkf, kPsLocal };
 
 // every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
 // is this one exactly
@@ -125,13 +140,18 @@ __device__ __forceinline__ bool near_int(double a, double e) { return fabs(a - r
 
 template <PsMode kMode>
 __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, double th, double eps,
-                                            const PsOut& out, [[maybe_unused]] const PsSim3& sx) {
+                                            const PsOut& out, [[maybe_unused]] const PsSim3& sx,
+                                            [[maybe_unused]] int th_on = 0) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode == kPsScw, kSim3 = kMode == kPsSim3;
-    constexpr bool kFkf = kMode == kPsFkf;
+    constexpr bool kLocal = kMode == kPsLocal;
+    // a Frame target: the reference's (fx * xc) * invz, inclusive bounds, a window truncated at both ends
+    constexpr bool kFkf = kMode == kPsFkf || kLocal;
+    constexpr bool kDepthFree = kMode == kPsFkf;  // no depth gate
     constexpr bool kRagged = kSim3 || kFkf;  // a 1-D grid over the chunk table, outputs flat over the items
     constexpr bool kBlocked = kScw || kFkf;
+    constexpr bool kRight = kFuse || kLocal;  // projects ur = u - bf / z
     __shared__ double s_u[kPsChunk], s_v[kPsChunk], s_eu[kPsChunk], s_ev[kPsChunk], s_r[kPsChunk];
-    __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, in k_fuse_search only
+    __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, where kRight only
     __shared__ int16_t s_x0[kPsChunk], s_x1[kPsChunk], s_y0[kPsChunk], s_y1[kPsChunk], s_lvl[kPsChunk];
     __shared__ uint8_t s_st[kPsChunk];
     const int tid = threadIdx.x;
@@ -171,7 +191,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
             if constexpr (kSim3) S = sx.f64 + (int64_t)srch * kPsSim3F64;
             const double* I = kSim3 ? S : K;
             const double fx = I[0], fy = I[1], cx = I[2], cy = I[3];
-            [[maybe_unused]] const double bf = kFuse ? K[4] : 0.0;  // only k_fuse_search reads the slot
+            [[maybe_unused]] const double bf = kRight ? K[4] : 0.0;  // the others do not read the slot
             const double minX = K[20], maxX = K[21], minY = K[22], maxY = K[23], winv = K[24], hinv = K[25],
                          lsf = K[26];
             const double p0 = P[0], p1 = P[1], p2 = P[2];
@@ -211,7 +231,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                         break;
                     }
                 }
-                if constexpr (kFkf) {
+                if constexpr (kDepthFree) {
                     // no depth gate: the sign of zc decides nothing, but within its bound of 0 nothing after it is
                     // known, and at zc == 0 the reference divides by zero; the caller's redo follows it there
                     if (zc == 0.0 || fabs(zc) < Ez) {
@@ -232,15 +252,18 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 u = fxx + cx;
                 v = fyy + cy;
                 [[maybe_unused]] double bz = 0.0;
-                if constexpr (kFuse) {
+                if constexpr (kRight) {
                     bz = bf * iz;
                     ur = u - bz;
                 }
                 // Frame's bounds are inclusive at both ends
                 const bool in = kFkf ? !(u < minX || u > maxX || v < minY || v > maxY)
                                      : minX <= u && u < maxX && minY <= v && v < maxY;
-                if constexpr (!kFkf) {
+                if constexpr (!kDepthFree) {
                     if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
+                    // k_local_search: the reference's NaN comparisons may let the point through its bounds
+                    if constexpr (kLocal)
+                        if (zc == 0.0) st = ORBFE_FUSE_MARGINAL;
                     if (zc == 0.0) break;  // not in the image (in is false), whatever xc and yc are
                 }
                 const double rz = Ez / (kFkf ? fabs(zc) : zc);
@@ -260,7 +283,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     Ev = fabs(fy) * Eyn + 4.0 * eps * Mv;
                 }
                 double sum;  // finite when everything phase 2 reads is
-                if constexpr (!kFuse) {
+                if constexpr (!kRight) {
                     sum = ((u + v) + Eu) + Ev;
                 } else {
                     Eur = (Eu + fabs(bf) * Eiz) + 4.0 * eps * (fabs(bz) + Mu);
@@ -297,7 +320,22 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 if (fabs(dist - minD) < Ed + eps * fabs(minD) || fabs(dist - maxD) < Ed + eps * fabs(maxD))
                     st = ORBFE_FUSE_MARGINAL;
                 if (dist < minD || dist > maxD) break;
-                if constexpr (!kSim3 && !kFkf) {  // neither has a viewing gate, and neither reads the normal
+                [[maybe_unused]] double vc = 0.0;
+                if constexpr (kLocal) {
+                    // the cosine itself is compared, with the search's limit and with 0.998 for the radius
+                    const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
+                    const double dot = (t0 + t1) + t2;
+                    vc = dot / dist;
+                    const double lim = sx.f64[srch];
+                    const double Evc = 5.0 * eps * ((fabs(t0) + fabs(t1)) + fabs(t2)) / dist + 8.0 * eps * fabs(vc);
+                    if (!isfinite(vc + Evc)) {
+                        st = ORBFE_FUSE_MARGINAL;
+                        break;
+                    }
+                    if (fabs(vc - lim) < Evc + eps * fabs(lim) || fabs(vc - 0.998) < Evc + eps * 0.998)
+                        st = ORBFE_FUSE_MARGINAL;
+                    if (vc < lim) break;
+                } else if constexpr (!kSim3 && !kFkf) {  // the others have no viewing gate and do not read the normal
                     const double t0 = po0 * P[3], t1 = po1 * P[4], t2 = po2 * P[5];
                     const double dot = (t0 + t1) + t2;
                     const double half = 0.5 * dist;
@@ -320,7 +358,15 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 }
                 const double cq = ceil(q);
                 const int level = cq < 0.0 ? 0 : (cq > (double)(levels - 1) ? levels - 1 : (int)cq);
-                r = th * scale[level];
+                if constexpr (kLocal) {
+                    // in view from here on, whatever becomes of the window
+                    lvl = level;
+                    double r0 = vc > 0.998 ? 2.5 : 4.0;
+                    if (th_on) r0 *= th;  // th == 1 multiplies nothing, as in the reference
+                    r = r0 * scale[level];
+                } else {
+                    r = th * scale[level];
+                }
                 const double ax = ((u - minX) - r) * winv, bx = ((u - minX) + r) * winv;
                 const double ay = ((v - minY) - r) * hinv, by = ((v - minY) + r) * hinv;
                 if (!isfinite((ax + bx) + (ay + by))) {
@@ -362,7 +408,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
         s_v[tid] = v;
         s_eu[tid] = Eu;
         s_ev[tid] = Ev;
-        if constexpr (kFuse) {
+        if constexpr (kRight) {
             s_ur[tid] = ur;
             s_eur[tid] = Eur;
         }
@@ -387,6 +433,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
     [[maybe_unused]] const uint8_t* blk = nullptr;
     if constexpr (kBlocked) {
         blk = kf.blocked ? kf.blocked + base : nullptr;
+        if constexpr (kLocal) uright = kf.u_right + base;
     } else if constexpr (kFuse) {
         uright = kf.u_right + base;
         is2 = kf.inv_sigma2 + kf.lvl_off[k];
@@ -397,10 +444,11 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
         const int level = s_lvl[j];
         unsigned st = s_st[j];
         unsigned key = kPsNone;
+        [[maybe_unused]] unsigned key2 = kPsNone;  // k_local_search: the second smallest key
         if (level >= 0) {
             const double u = s_u[j], v = s_v[j], Eu = s_eu[j], Ev = s_ev[j], r = s_r[j];
             [[maybe_unused]] double ur = 0.0, Eur = 0.0;
-            if constexpr (kFuse) {
+            if constexpr (kRight) {
                 ur = s_ur[j];
                 Eur = s_eur[j];
             }
@@ -424,7 +472,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     if (fabs(fabs(dx) - r) < Edx + er_r || fabs(fabs(dy) - r) < Edy + er_r) st = ORBFE_FUSE_MARGINAL;
                     if (!(fabs(dx) < r && fabs(dy) < r)) continue;
                     const int o = oct[f];
-                    if (o < level - 1 || o > level + (kFkf ? 1 : 0)) continue;
+                    if (o < level - 1 || o > level + (kFkf && !kLocal ? 1 : 0)) continue;
                     if constexpr (kFuse) {
                         const double kr = uright[f];
                         const double ex = u - kx, ey = v - ky;
@@ -446,13 +494,34 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                         if (!(fabs(chi - T) >= Echi + eps * T)) st = ORBFE_FUSE_MARGINAL;  // a NaN marks too
                         if (chi > T) continue;
                     }
+                    if constexpr (kLocal) {
+                        // the per-candidate stereo gate: |ur - uR| > r leaves a feature with a right coordinate out
+                        const double kr = uright[f];
+                        if (kr > 0.0) {
+                            const double er = fabs(ur - kr);
+                            const double Eer = Eur + 2.0 * eps * (fabs(kr) + fabs(ur));
+                            if (fabs(er - r) < Eer + er_r) st = ORBFE_FUSE_MARGINAL;
+                            if (er > r) continue;
+                        }
+                    }
                     const unsigned d = hamming256(desc[2 * f], desc[2 * f + 1], qa, qb);
-                    key = min(key, (d << 16) | (unsigned)pos);
+                    const unsigned c = (d << 16) | (unsigned)pos;
+                    if constexpr (kLocal) {
+                        // positions differ, so keys do: the lane holds the two smallest of what it has seen
+                        key2 = min(key2, max(key, c));
+                    }
+                    key = min(key, c);
                 }
             }
 #pragma unroll
             for (int o = kPsGroup / 2; o; o >>= 1) {
-                key = min(key, (unsigned)__shfl_xor((int)key, o, kPsGroup));
+                const unsigned ok = (unsigned)__shfl_xor((int)key, o, kPsGroup);
+                if constexpr (kLocal) {
+                    // the two smallest of two disjoint sets, each given by its two smallest
+                    const unsigned ok2 = (unsigned)__shfl_xor((int)key2, o, kPsGroup);
+                    key2 = min(max(key, ok), min(key2, ok2));
+                }
+                key = min(key, ok);
                 st |= (unsigned)__shfl_xor((int)st, o, kPsGroup);
             }
         }
@@ -461,6 +530,12 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
             out.best_idx[at] = key == kPsNone ? -1 : cidx[key & 0xFFFFu];
             out.best_dist[at] = key == kPsNone ? -1 : (int)(key >> 16);
             out.status[at] = (uint8_t)st;
+            if constexpr (kLocal) {
+                out.second_idx[at] = key2 == kPsNone ? -1 : cidx[key2 & 0xFFFFu];
+                out.second_dist[at] = key2 == kPsNone ? -1 : (int)(key2 >> 16);
+                out.level[at] = level;
+                out.in_view[at] = level >= 0;
+            }
         }
     }
 }
@@ -483,6 +558,13 @@ __global__ __launch_bounds__(kPsChunk) void k_sim3_search(PsKfs kf, PsPts pt, do
 __global__ __launch_bounds__(kPsChunk) void k_fkf_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out,
                                                          PsSim3 sx) {
     proj_search<kPsFkf>(kf, pt, th, eps, out, sx);
+}
+
+// the same grid; sx.f64 holds one double per search, the viewing cosine's limit; th multiplies the radius only
+// where th_on is set
+__global__ __launch_bounds__(kPsChunk) void k_local_search(PsKfs kf, PsPts pt, double th, double eps, PsOut out,
+                                                           PsSim3 sx, int th_on) {
+    proj_search<kPsLocal>(kf, pt, th, eps, out, sx, th_on);
 }
 
 }  // namespace orbfe
@@ -513,14 +595,16 @@ std::string at_kf(int32_t k, const std::string& what) { return "keyframe " + std
 
 // what orbfe_sim3_search and orbfe_fkf_search have besides the keyframes and the point table
 struct Sim3In {
-    const double* f64;  // orbfe_fkf_search: null
+    const double* f64;  // orbfe_fkf_search: null; orbfe_local_search: the viewing cosine's limit per search
     const int32_t* kf;
     const int64_t* off;
     int32_t n;
     const int32_t* item_pt;
+    int th_on = 0;  // orbfe_local_search only
 };
 
-// All four entries: validate, stage, launch, download.  Not kPsFuse: u_right and inv_sigma2 are not looked at and
+// All five entries: validate, stage, launch, download.  kPsLocal is kPsFkf with u_right, slot 4 and the normal read,
+// one scalar per search and four more outputs.  Otherwise, not kPsFuse: u_right and inv_sigma2 are not looked at and
 // slot 4 of a keyframe's scalars may hold anything.  kPsScw, kPsFkf: blocked may be null (nothing is blocked);
 // otherwise blocked is not looked at.  kPsSim3, kPsFkf: sx is the searches, slots 3-5 of a point's scalars may hold
 // anything, out_stride is not looked at and the outputs are flat over the items; kPsSim3 alone has search scalars and
@@ -533,7 +617,11 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride,
             [[maybe_unused]] const Sim3In* sx = nullptr) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode != kPsFuse, kSim3 = kMode == kPsSim3;
-    constexpr bool kRagged = kSim3 || kMode == kPsFkf, kBlocked = kMode == kPsScw || kMode == kPsFkf;
+    constexpr bool kLocal = kMode == kPsLocal;
+    constexpr bool kRight = kFuse || kLocal;  // u_right and slot 4 (bf) are read
+    constexpr bool kRagged = kSim3 || kMode == kPsFkf || kLocal;
+    constexpr bool kBlocked = kMode == kPsScw || kMode == kPsFkf || kLocal;
+    constexpr size_t kOutI32 = kLocal ? 5 : 2, kOutU8 = kLocal ? 2 : 1;  // output arrays per item
     if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
     if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
     if (!std::isfinite(th) || !std::isfinite(eps) || eps < 0.0)
@@ -549,12 +637,14 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": srch_off must not decrease");
         n_items = sx->off[sx->n];
         if (n_items == 0) return;
-        if ((kSim3 && !sx->f64) || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
+        if (((kSim3 || kLocal) && !sx->f64) || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
         for (int32_t q = 0; q < sx->n; ++q) {
             if (sx->kf[q] < 0 || sx->kf[q] >= n_kf)
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the target is outside the keyframes");
             if (kSim3 && !all_finite(sx->f64 + (int64_t)q * ORBFE_SIM3_F64, ORBFE_SIM3_F64))
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": a scalar is not finite");
+            if (kLocal && !std::isfinite(sx->f64[q]))
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the viewing cosine's limit is not finite");
         }
         for (int64_t i = 0; i < n_items; ++i)
             if (sx->item_pt[i] < 0 || sx->item_pt[i] >= n_pts)
@@ -565,6 +655,9 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     if (!kf_f64 || !kf_i32 || !off || !cell_at || !idx_at || !lvl_off || !cell_off || !scale ||
         (!kScw && !inv_sigma2) || !pt_f64 || !pt_desc32 || !out || !out->best_idx || !out->best_dist || !out->status)
         throw Error(ORBFE_EINVAL, "null argument");
+    if constexpr (kLocal)
+        if (!out->in_view || !out->level || !out->second_idx || !out->second_dist)
+            throw Error(ORBFE_EINVAL, "null argument");
     if (!kRagged && out_stride < n_pts) throw Error(ORBFE_EINVAL, "out_stride is below the point count");
     if (off[0] != 0 || cell_at[0] != 0 || idx_at[0] != 0 || lvl_off[0] != 0)
         throw Error(ORBFE_EINVAL, "off[0], cell_at[0], idx_at[0] and lvl_off[0] must be 0");
@@ -580,7 +673,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
                                                    std::to_string(ORBFE_BOW_MAX_FRAME) + " per keyframe"));
         // slot 4 is bf, which only k_fuse_search reads; k_sim3_search reads none of the slots before the bounds
         const double* Kk = kf_f64 + (int64_t)k * ORBFE_FUSE_KF_F64;
-        if (!((kSim3 || (all_finite(Kk, 4) && (kScw || std::isfinite(Kk[4])) && all_finite(Kk + 5, 15))) &&
+        if (!((kSim3 || (all_finite(Kk, 4) && (!kRight || std::isfinite(Kk[4])) && all_finite(Kk + 5, 15))) &&
               all_finite(Kk + 20, ORBFE_FUSE_KF_F64 - 20)))
             throw Error(ORBFE_EINVAL, at_kf(k, "a scalar is not finite"));
         const int64_t cols = kf_i32[3 * k], rows = kf_i32[3 * k + 1], levels = kf_i32[3 * k + 2];
@@ -591,8 +684,8 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
         if (nc != cols * rows + 1) throw Error(ORBFE_EINVAL, at_kf(k, "the grid needs columns * rows + 1 cell offsets"));
         if (!(all_finite(scale + lvl_off[k], nl) && (kScw || all_finite(inv_sigma2 + lvl_off[k], nl))))
             throw Error(ORBFE_EINVAL, at_kf(k, "a level table entry is not finite"));
-        if (n > 0 && (!xy || !octave || (!kScw && !u_right) || !desc32)) throw Error(ORBFE_EINVAL, "null argument");
-        if (n > 0 && !(all_finite(xy + 2 * off[k], 2 * n) && (kScw || all_finite(u_right + off[k], n))))
+        if (n > 0 && (!xy || !octave || (kRight && !u_right) || !desc32)) throw Error(ORBFE_EINVAL, "null argument");
+        if (n > 0 && !(all_finite(xy + 2 * off[k], 2 * n) && (!kRight || all_finite(u_right + off[k], n))))
             throw Error(ORBFE_EINVAL, at_kf(k, "a keypoint coordinate is not finite"));
         for (int64_t i = 0; i < n; ++i) {
             const int32_t o = octave[off[k] + i];
@@ -609,7 +702,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
         }
     }
-    if constexpr (kRagged) {
+    if constexpr (kRagged && !kLocal) {
         for (int64_t i = 0; i < n_pts; ++i)  // slots 3-5, the normal, are not read
             if (!(all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64, 3) && all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64 + 6, 3)))
                 throw Error(ORBFE_EINVAL, "a point scalar is not finite");
@@ -623,7 +716,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     const size_t n = (size_t)off[n_kf], nc = (size_t)cell_at[n_kf], ni = (size_t)idx_at[n_kf],
                  nl = (size_t)lvl_off[n_kf];
     // what only one variant stages has no room in the other's buffers
-    const size_t n_ur = kScw ? 0 : n, n_is2 = kScw ? 0 : nl, n_blk = kBlocked ? pad_to(n, 16) : 0;
+    const size_t n_ur = kRight ? n : 0, n_is2 = kScw ? 0 : nl, n_blk = kBlocked ? pad_to(n, 16) : 0;
     const bool has_blocked = kBlocked && blocked != nullptr && n > 0;
     Searcher& m = searcher<kMode>();
     std::lock_guard<std::mutex> lk(m.mu);
@@ -641,11 +734,11 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     }
     hipStream_t s = m.t.get();
     // descriptors are read as uint4: both blocks start on 16 bytes
-    m.d_u8.ensure(pad_to(n * 32, 16) + pad_to(np * 32, 16) + n_blk + n_out);
+    m.d_u8.ensure(pad_to(n * 32, 16) + pad_to(np * 32, 16) + n_blk + kOutU8 * n_out);
     m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 +
-                   (kSim3 ? ns * ORBFE_SIM3_F64 : 0));
+                   (kSim3 ? ns * ORBFE_SIM3_F64 : kLocal ? ns : 0));
     m.d_i64.ensure(4 * (nk + 1) + (kRagged ? ns + 1 + 2 * n_chunk : 0));
-    m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + 2 * n_out);
+    m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + kOutI32 * n_out);
     uint8_t* d_desc = m.d_u8.p;
     uint8_t* d_pdesc = d_desc + pad_to(n * 32, 16);
     uint8_t* d_blk = d_pdesc + pad_to(np * 32, 16);
@@ -694,11 +787,12 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     [[maybe_unused]] PsSim3 dsx{};
     if constexpr (kRagged) {
         if constexpr (kSim3) up(d_sx, sx->f64, ns * ORBFE_SIM3_F64 * sizeof(double));
+        if constexpr (kLocal) up(d_sx, sx->f64, ns * sizeof(double));
         up(d_soff, sx->off, (ns + 1) * sizeof(int64_t));
         up(d_chunk, m.h_chunk.data(), 2 * n_chunk * sizeof(int64_t));
         up(d_skf, sx->kf, ns * sizeof(int32_t));
         up(d_item, sx->item_pt, n_out * sizeof(int32_t));
-        dsx = PsSim3{kSim3 ? d_sx : nullptr, d_skf, d_soff, d_item, d_chunk};
+        dsx = PsSim3{kSim3 || kLocal ? d_sx : nullptr, d_skf, d_soff, d_item, d_chunk};
     }
     PsKfs kf{};
     kf.f64 = d_kf;
@@ -709,7 +803,7 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     kf.lvl_off = d_lvl;
     kf.xy = d_xy;
     kf.scale = d_scale;
-    kf.u_right = kScw ? nullptr : d_ur;
+    kf.u_right = kRight ? d_ur : nullptr;
     kf.inv_sigma2 = kScw ? nullptr : d_is2;
     kf.octave = d_oct;
     kf.cell_off = d_coff;
@@ -717,9 +811,14 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     kf.desc = d_desc;
     kf.blocked = has_blocked ? d_blk : nullptr;
     const PsPts pt{d_pt, d_pdesc, n_pts};
-    const PsOut d{d_bi, d_bd, d_st, out_stride};
+    // k_local_search: second_idx, second_dist and level follow best_dist, in_view follows status
+    const PsOut d{d_bi, d_bd, d_st, out_stride, kLocal ? d_bd + n_out : nullptr, kLocal ? d_bd + 2 * n_out : nullptr,
+                  kLocal ? d_bd + 3 * n_out : nullptr, kLocal ? d_st + n_out : nullptr};
     m.t.begin(s);
-    if constexpr (kRagged) {
+    if constexpr (kLocal) {
+        hipLaunchKernelGGL(k_local_search, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx,
+                           sx->th_on);
+    } else if constexpr (kRagged) {
         constexpr auto kernel = kSim3 ? k_sim3_search : k_fkf_search;
         hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx);
     } else {
@@ -731,16 +830,22 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     m.t.end(s);
     // the rows come back whole into staging; only the entries the kernel wrote, [0, n_pts) of each row, reach
     // the caller's arrays
-    m.h_i32.resize(2 * n_out);
-    m.h_st.resize(n_out);
-    HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, 2 * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, n_out, hipMemcpyDeviceToHost, s));
+    m.h_i32.resize(kOutI32 * n_out);
+    m.h_st.resize(kOutU8 * n_out);
+    HIPCK(hipMemcpyAsync(m.h_i32.data(), d_bi, kOutI32 * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(m.h_st.data(), d_st, kOutU8 * n_out, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     m.t.last_ms = m.t.elapsed_ms();
     if constexpr (kRagged) {  // every item was written
         std::memcpy(out->best_idx, m.h_i32.data(), n_out * sizeof(int32_t));
         std::memcpy(out->best_dist, m.h_i32.data() + n_out, n_out * sizeof(int32_t));
         std::memcpy(out->status, m.h_st.data(), n_out);
+        if constexpr (kLocal) {
+            std::memcpy(out->second_idx, m.h_i32.data() + 2 * n_out, n_out * sizeof(int32_t));
+            std::memcpy(out->second_dist, m.h_i32.data() + 3 * n_out, n_out * sizeof(int32_t));
+            std::memcpy(out->level, m.h_i32.data() + 4 * n_out, n_out * sizeof(int32_t));
+            std::memcpy(out->in_view, m.h_st.data() + n_out, n_out);
+        }
         return;
     }
     for (size_t k = 0; k < nk; ++k) {
@@ -825,6 +930,24 @@ int orbfe_fkf_search(const double* kf_f64, const int32_t* kf_i32, const int64_t*
 
 int orbfe_fkf_search_last_ms(float* ms) {
     return guarded([&] { last_ms<kPsFkf>(ms); });
+}
+
+int orbfe_local_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                       const int32_t* octave, const double* u_right, const uint8_t* desc32, const uint8_t* blocked,
+                       const int64_t* cell_at, const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx,
+                       const int64_t* lvl_off, const double* scale, int32_t n_kf, const double* pt_f64,
+                       const uint8_t* pt_desc32, int64_t n_pts, const double* srch_limit, const int32_t* srch_kf,
+                       const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt, double th, int32_t th_on,
+                       double eps, const orbfe_local_out* out) {
+    return guarded([&] {
+        const Sim3In sx{srch_limit, srch_kf, srch_off, n_srch, item_pt, th_on != 0};
+        search<kPsLocal>(kf_f64, kf_i32, off, xy, octave, u_right, desc32, blocked, cell_at, cell_off, idx_at,
+                         cell_idx, lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, th, eps, out, 0, &sx);
+    });
+}
+
+int orbfe_local_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<kPsLocal>(ms); });
 }
 
 }  // extern "C"

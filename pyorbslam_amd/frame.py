@@ -292,3 +292,109 @@ def install(frame_cls, copy: bool = True, pair: bool = True) -> None:
         frame_cls.ExtractORB = extract_orb
     if copy:
         frame_cls.copy = frame_copy
+
+
+def is_in_frustum_one(frame, pMP, viewing_cos_limit) -> bool:
+    """Frame.is_in_frustum (Frame.py:328-371) for one map point, with the reference's expressions on the objects."""
+    pMP.mbTrackInView = False
+    with np.errstate(all="ignore"):
+        P = pMP.get_world_pos()
+        Pc = frame.mRcw @ P + frame.mtcw
+        PcX = Pc[0]
+        PcY = Pc[1]
+        PcZ = Pc[2]
+        if PcZ < 0.0:
+            return False
+        invz = 1.0 / PcZ
+        u = frame.fx * PcX * invz + frame.cx
+        v = frame.fy * PcY * invz + frame.cy
+        if u < frame.mnMinX or u > frame.mnMaxX:
+            return False
+        if v < frame.mnMinY or v > frame.mnMaxY:
+            return False
+        max_distance = pMP.get_max_distance_invariance()
+        min_distance = pMP.get_min_distance_invariance()
+        PO = P - frame.mOw
+        dist = np.linalg.norm(PO)
+        if dist < min_distance or dist > max_distance:
+            return False
+        Pn = pMP.get_normal()
+        view_cos = (PO.T).dot(Pn) / dist
+        if view_cos[0] < viewing_cos_limit:
+            return False
+        n_predicted_level = pMP.predict_scale(dist, frame)
+        pMP.mbTrackInView = True
+        pMP.mTrackProjX = u
+        pMP.mTrackProjXR = u - frame.mbf * invz
+        pMP.mTrackProjY = v
+        pMP.mnTrackScaleLevel = n_predicted_level
+        pMP.mTrackViewCos = view_cos
+    return True
+
+
+def _uniform_31(arrs) -> bool:
+    """Whether arrs are ndarrays of shape (3, 1) and one float dtype: np.concatenate then stacks them exactly."""
+    return (bool(arrs) and {type(a) for a in arrs} == {np.ndarray} and {a.shape for a in arrs} == {(3, 1)}
+            and len({a.dtype for a in arrs}) == 1 and arrs[0].dtype.kind == "f")
+
+
+def is_in_frustum_many(frame, mps, viewing_cos_limit) -> list:
+    """[frame.is_in_frustum(pMP, viewing_cos_limit) for pMP in mps] of the reference (Frame.py:328-371), leaving on
+    every point what that loop leaves, values and types included: mbTrackInView, and on a point in view mTrackProjX,
+    mTrackProjY, mTrackProjXR (shape (1,) arrays of the promoted dtype), mnTrackScaleLevel (what the point's
+    predict_scale returns) and mTrackViewCos (a shape (1, 1) array).  Computed on the host with the reference's
+    expressions stacked: one matmul for Rcw @ P of every point, as search_by_projection_f_f's, and one each for
+    PO . PO (np.linalg.norm is sqrt(x.dot(x)) of the ravelled vector) and PO . Pn, which give the per-point BLAS
+    products; the element-wise operations keep the reference's order, operands and promotions; a comparison of a
+    distance with a point's own bound runs per point on NumPy scalars, since a stacked bound would promote it.  Goes
+    point by point (is_in_frustum_one) when the positions, or the normals of the points that get that far, are not
+    arrays of one shape (3, 1) and dtype.  No device is involved."""
+    mps = list(mps)
+    n = len(mps)
+    if n == 0:
+        return []
+    pos = [p.get_world_pos() for p in mps]
+    if not _uniform_31(pos):
+        return [is_in_frustum_one(frame, p, viewing_cos_limit) for p in mps]
+    out = [False] * n
+    with np.errstate(all="ignore"):
+        P = np.concatenate(pos).reshape(n, 3, 1)
+        Pc = frame.mRcw @ P + frame.mtcw
+        PcX, PcY, PcZ = Pc[:, 0], Pc[:, 1], Pc[:, 2]  # (n, 1): a row is the reference's Pc[0], shape (1,)
+        invz = 1.0 / PcZ
+        u = frame.fx * PcX * invz + frame.cx
+        v = frame.fy * PcY * invz + frame.cy
+        gone = (PcZ < 0.0) | (u < frame.mnMinX) | (u > frame.mnMaxX) | (v < frame.mnMinY) | (v > frame.mnMaxY)
+        idx = np.flatnonzero(~gone[:, 0]).tolist()
+        if idx:
+            sub = [mps[i] for i in idx]
+            max_d = [p.get_max_distance_invariance() for p in sub]
+            min_d = [p.get_min_distance_invariance() for p in sub]
+            PO = P[idx] - frame.mOw
+            dist = np.sqrt(PO.transpose(0, 2, 1) @ PO)[:, 0, 0]
+            ok = [not (d < lo or d > hi) for d, lo, hi in zip(dist, min_d, max_d)]
+            keep = np.flatnonzero(ok)
+            idx, sub = [idx[k] for k in keep.tolist()], [sub[k] for k in keep.tolist()]
+            PO, dist = PO[keep], dist[keep]
+        if idx:
+            nrm = [p.get_normal() for p in sub]
+            if not _uniform_31(nrm):
+                return [is_in_frustum_one(frame, p, viewing_cos_limit) for p in mps]
+            view_cos = (PO.transpose(0, 2, 1) @ np.concatenate(nrm).reshape(len(nrm), 3, 1)) / dist.reshape(-1, 1, 1)
+            xr = u - frame.mbf * invz
+            seen = (~(view_cos[:, 0, 0] < viewing_cos_limit)).tolist()
+        for p in mps:
+            p.mbTrackInView = False
+        if idx:
+            for k, (i, p) in enumerate(zip(idx, sub)):
+                if not seen[k]:
+                    continue
+                level = p.predict_scale(dist[k], frame)
+                p.mbTrackInView = True
+                p.mTrackProjX = u[i]
+                p.mTrackProjXR = xr[i]
+                p.mTrackProjY = v[i]
+                p.mnTrackScaleLevel = level
+                p.mTrackViewCos = view_cos[k]
+                out[i] = True
+    return out

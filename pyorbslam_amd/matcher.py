@@ -36,7 +36,9 @@ fuse_kf_scw_mp_many and search_by_projection_ckf_scw_mp (k_scw_search) do it for
 and search_by_sim3 / search_by_sim3_many (k_sim3_search) for its mutual search: both directions of every candidate
 pair in one launch, nothing to replay in order.  search_by_projection_f_kf_f / _f_kf_f_many (k_fkf_search) do it
 for Tracking.relocalization's search into a frame, which assigns into the frame it searches: one launch, then the
-assignments replayed in list order.
+assignments replayed in list order.  search_local_points / search_local_points_many (k_local_search) do it for
+Tracking.search_local_points: Frame.is_in_frustum over the local map and search_by_projection_f_p in one launch, the
+attributes written by frame.is_in_frustum_many on the host, the assignments replayed in list order.
 """
 from __future__ import annotations
 
@@ -736,6 +738,70 @@ def fkf_search_arrays(kf_f64, kf_i32, off, xy, octave, desc, blocked, cell_at, c
                           scale, pt_f64, pt_desc, th, eps, blocked=blocked, fkf=(srch_kf, srch_off, item_pt))
 
 
+LOCAL_OUTPUTS = ("in_view", "level", "best_idx", "best_dist", "second_idx", "second_dist", "status")
+
+
+def local_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, blocked, cell_at, cell_off, idx_at, cell_idx,
+                        lvl_off, scale, pt_f64, pt_desc, srch_limit, srch_kf, srch_off, item_pt, th, th_on,
+                        eps) -> dict:
+    """orbfe_local_search (k_local_search, include/orbfe.h): Frame.is_in_frustum (Frame.py:328-371) and the search
+    half of ORBMatcher.search_by_projection_f_p (ORBMatcher.py:215-283) for many (frame, local map) searches in one
+    launch.  The target arrays are fkf_search_arrays' with u_right (<= 0: no stereo gate) and the bf slot of kf_f64
+    read; pt_f64 (P, 9) / pt_desc (P, 32) are one shared point table, the normal read.  Search s has the viewing
+    cosine's limit srch_limit[s], the target srch_kf[s] and the items [srch_off[s], srch_off[s + 1]) of item_pt.  th
+    multiplies the radius only where th_on is true (the caller's th != 1.0).  Returns, flat over the items: in_view
+    uint8, level int32 (-1: not in view), best_idx, best_dist, second_idx, second_dist int32 (-1: none) and status
+    uint8 (ORBFE_FUSE_MARGINAL)."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
+    kf_i32 = np.ascontiguousarray(kf_i32, np.int32).reshape(-1, 3)
+    pt_f64 = np.ascontiguousarray(pt_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
+    pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
+    off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
+    xy, u_right, scale, srch_limit = (arr(a, np.float64) for a in (xy, u_right, scale, srch_limit))
+    octave, cell_off, cell_idx = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32)
+    desc, blocked = arr(desc, np.uint8), arr(blocked, np.uint8)
+    n_kf, n_pts = len(kf_f64), len(pt_f64)
+    if len(kf_i32) != n_kf or len(pt_desc) != n_pts:
+        raise ValueError("kf_i32 / pt_desc do not cover the keyframes / points")
+    for a in (off, cell_at, idx_at, lvl_off):
+        if a is None or len(a) != n_kf + 1:
+            raise ValueError("an offset array does not have one entry per keyframe and one more")
+    if n_kf:
+        n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
+        for a, size in ((xy, 2 * n), (octave, n), (u_right, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni),
+                        (scale, nl)):
+            if size > 0 and (a is None or a.size < size):
+                raise ValueError("a per-keyframe array is shorter than its offsets say")
+        if blocked is not None and blocked.size < n:
+            raise ValueError("blocked does not have one byte per feature")
+    n_srch = 0 if srch_kf is None else int(np.size(srch_kf))
+    srch_kf, srch_off, item_pt = arr(srch_kf, np.int32), arr(srch_off, np.int64), arr(item_pt, np.int32)
+    if srch_kf is None or srch_off is None or srch_off.size != n_srch + 1 or (
+            n_srch and (srch_limit is None or srch_limit.size != n_srch)):
+        raise ValueError("srch_limit / srch_kf / srch_off do not cover the searches")
+    n_items = int(srch_off[-1])
+    if n_items > 0 and (item_pt is None or item_pt.size < n_items):
+        raise ValueError("item_pt is shorter than srch_off says")
+    n_items = max(n_items, 0)
+    res = {k: (np.zeros(n_items, np.uint8) if k in ("in_view", "status") else np.full(n_items, -1, np.int32))
+           for k in LOCAL_OUTPUTS}
+    out = _lib.LocalOut(**{k: v.ctypes.data for k, v in res.items()})
+    call("orbfe_local_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(u_right), ptr(desc),
+         ptr(blocked), ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), n_kf,
+         ptr(pt_f64), ptr(pt_desc), n_pts, ptr(srch_limit), ptr(srch_kf), ptr(srch_off), n_srch, ptr(item_pt),
+         float(th), 1 if th_on else 0, float(eps), C.byref(out))
+    return res
+
+
+def local_search_last_ms() -> float:
+    """Kernel time of the last local_search_arrays call (ms, HIP events)."""
+    ms = C.c_float(0.0)
+    call("orbfe_local_search_last_ms", C.byref(ms))
+    return float(ms.value)
+
+
 # eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
 # float32 (2^-24 is its unit roundoff) and the 2^-48 class of k_tri_match for float64
 FUSE_EPS_F32 = 2.0 ** -23
@@ -743,6 +809,7 @@ FUSE_EPS_F64 = 2.0 ** -48
 _POSE_DT = (np.dtype(np.float32), np.dtype(np.float64))
 _F32_DT = np.dtype(np.float32)
 _TH_SET = frozenset((int, float, np.float64))
+_DIST_SET = frozenset((float, np.float64, np.float32))
 _fuse_cache = weakref.WeakKeyDictionary()
 
 
@@ -860,7 +927,7 @@ def _fuse_frame(kf):
     return f
 
 
-def _fkf_frame(F):
+def _fkf_frame(F, int_bounds=False):
     """Array form of a Frame for k_fkf_search, with the surface search_by_projection_f_kf_f and
     Frame.get_features_in_area read (Frame.py): the _FuseFrame of _fuse_frame without right coordinates and inverse
     sigma squares, the grid FRAME_GRID_COLS x FRAME_GRID_ROWS, the bf slot 0.0 (not read), the pose slots from mTcw
@@ -868,7 +935,9 @@ def _fkf_frame(F):
     express the frame (the caller then takes the host body): an attribute of that surface is missing, intrinsics or
     grid parameters are not plain doubles, mTcw is not a finite 4 x 4 float32 / float64 array or the centre it
     gives is not finite, and what _fuse_static and _fuse_frame refuse in a keyframe's features, grid and scale
-    table."""
+    table.  int_bounds (k_local_search): an image bound may also be a plain int below 2^53, which every comparison and
+    difference the reference makes with it takes at its exact value (Tracking passes the image's width and height
+    as mnMaxX and mnMaxY where there is no distortion)."""
     try:
         sc = (F.fx, F.fy, F.cx, F.cy)
         gr = (F.mnMinX, F.mnMaxX, F.mnMinY, F.mnMaxY, F.mfGridElementWidthInv, F.mfGridElementHeightInv,
@@ -876,6 +945,8 @@ def _fkf_frame(F):
         dims, levels, sf, T = (F.FRAME_GRID_COLS, F.FRAME_GRID_ROWS), F.mnScaleLevels, F.mvScaleFactors, F.mTcw
     except AttributeError:
         return None
+    if int_bounds and all(type(b) is not int or abs(b) < 2 ** 53 for b in gr[:4]):
+        gr = tuple(float(b) if type(b) is int else b for b in gr[:4]) + gr[4:]
     if not (set(map(type, sc)) <= _F64_SET and set(map(type, gr)) <= _F64_SET):
         return None
     if type(levels) not in _INT_SET or levels <= 0:
@@ -911,18 +982,53 @@ def _fkf_frame(F):
     return f
 
 
-def _fuse_point(pMP, normal=True):
+def _local_frame(F):
+    """Array form of a Frame for k_local_search, with the surface Frame.is_in_frustum and search_by_projection_f_p
+    read: _fkf_frame's (an image bound may be a plain int), with the bf slot from mbf, the pose slots from mRcw, mtcw and mOw (what is_in_frustum
+    projects with; set_pose derives them from mTcw) and the right coordinates of mvuRight.  None when _fkf_frame
+    refuses the frame, when one of those attributes is missing, when mbf is not a plain finite double, when a pose part
+    is not a finite float32 / float64 array of its shape, or when mvuRight does not hold one int / float / np.float32 /
+    np.float64 per feature."""
+    f = _fkf_frame(F, int_bounds=True)
+    if f is None:
+        return None
+    try:
+        bf, parts, ur = F.mbf, (F.mRcw, F.mtcw, F.mOw), F.mvuRight
+    except AttributeError:
+        return None
+    if type(bf) not in _F64_SET or not np.isfinite(bf):
+        return None
+    R, t, O = _pose_part(parts[0], (3, 3)), _pose_part(parts[1], (3, 1)), _pose_part(parts[2], (3, 1))
+    if R is None or t is None or O is None:
+        return None
+    if len(ur) != len(f.xy) or not set(map(type, ur)) <= _UR_SET:
+        return None
+    u_right = _u_right(F)
+    if not np.isfinite(u_right).all():
+        return None
+    f.f64 = f.f64.copy()
+    f.f64[4] = bf
+    f.f64[5:20] = R[0] + t[0] + O[0]
+    f.u_right = u_right
+    f.f32 = R[1] or t[1] or O[1]
+    return f
+
+
+def _fuse_point(pMP, normal=True, f32_dist=False):
     """(9 doubles, descriptor row, any float32) of a map point for k_fuse_search, or None when the arrays cannot
     express it: a position or normal that is not a finite (3, 1) float32 / float64 array, distances that are not
     plain doubles, a descriptor that is not 32 bytes of uint8.  normal False (k_fkf_search, whose reference never
-    asks for it): get_normal is not called and the slots hold zeros."""
+    asks for it): get_normal is not called and the slots hold zeros.  f32_dist (k_local_search): a distance may also
+    be an np.float32, which a map point made from a float32 pose holds; it is widened exactly, as the reference's
+    comparison with a float64 distance widens it (against a float32 distance the caller's eps is float32's)."""
     p = _pose_part(pMP.get_world_pos(), (3, 1))
     nrm = _pose_part(pMP.get_normal(), (3, 1)) if normal else ([0.0, 0.0, 0.0], False)
     if p is None or nrm is None:
         return None
     d3 = (pMP.get_min_distance_invariance(), pMP.get_max_distance_invariance(), pMP.mfMaxDistance)
-    if not set(map(type, d3)) <= _F64_SET or not all(map(np.isfinite, d3)):
+    if not set(map(type, d3)) <= (_DIST_SET if f32_dist else _F64_SET) or not all(map(np.isfinite, d3)):
         return None
+    d3 = tuple(map(float, d3))
     d = pMP.get_descriptor()
     if not (type(d) is np.ndarray and d.dtype == _U8_DT and d.size == 32):
         return None
@@ -1671,7 +1777,7 @@ class ORBMatcher:
         return f, (Rcw, tcw, Ow)
 
     @staticmethod
-    def _search_points(vpPoints, skip, normal=True):
+    def _search_points(vpPoints, skip, normal=True, f32_dist=False):
         """The points once: (slot per list position, rows, descriptor rows, any float32).  slot >= 0 is the row sent
         to the device, -1 not expressible (_fuse_point, with its normal), -2 skipped by skip(pMP)."""
         slot, rows, descs, f32 = [], [], [], False
@@ -1679,7 +1785,7 @@ class ORBMatcher:
             if skip(pMP):
                 slot.append(-2)
                 continue
-            pt = _fuse_point(pMP, normal)
+            pt = _fuse_point(pMP, normal, f32_dist)
             if pt is None:
                 slot.append(-1)
                 continue
@@ -1690,10 +1796,11 @@ class ORBMatcher:
         return slot, rows, descs, f32
 
     @staticmethod
-    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None, fkf=None):
+    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None, fkf=None, local=None):
         """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse), of
         scw_search_arrays (with blocked), of sim3_search_arrays (with sim3 = (srch_f64, srch_kf, srch_off,
-        item_pt)) or of fkf_search_arrays (with blocked and fkf = (srch_kf, srch_off, item_pt))."""
+        item_pt)), of fkf_search_arrays (with blocked and fkf = (srch_kf, srch_off, item_pt)) or of
+        local_search_arrays (with blocked and local = (srch_limit, srch_kf, srch_off, item_pt, th_on))."""
         def offs(lens):
             o = np.zeros(len(fr) + 1, np.int64)
             np.cumsum(lens, out=o[1:])
@@ -1710,6 +1817,9 @@ class ORBMatcher:
             return sim3_search_arrays(*head, cat("desc"), *grid, *pts[:2], *sim3, *pts[2:])
         if fkf is not None:
             return fkf_search_arrays(*head, cat("desc"), blocked, *grid, *pts[:2], *fkf, *pts[2:])
+        if local is not None:
+            return local_search_arrays(*head, cat("u_right"), cat("desc"), blocked, *grid, *pts[:2], *local[:4], th,
+                                       local[4], pts[3])
         return scw_search_arrays(*head, cat("desc"), blocked, *grid, *pts)
 
     def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
@@ -2672,6 +2782,259 @@ class ORBMatcher:
                 for k, n in zip(take, self._fkf_jobs([jobs[k] + (packed[k],) for k in take], th, ORBdist)):
                     res[k] = n
         return [self.search_by_projection_f_kf_f(*j, th, ORBdist) if r is None else r for j, r in zip(jobs, res)]
+
+    # Tracking.py:439-468
+    def _local_job(self, frame, th, viewing_cos_limit):
+        """_local_frame(frame) when one search_local_points can run on the device, else None: see the conditions
+        there."""
+        if type(self).radius_by_viewing_cos is not ORBMatcher.radius_by_viewing_cos:
+            return None
+        if not (type(th) in _TH_SET and np.isfinite(th) and type(viewing_cos_limit) in _TH_SET
+                and np.isfinite(viewing_cos_limit)):
+            return None
+        f = _local_frame(frame)
+        if f is None:
+            return None
+        mvp = frame.mvpMapPoints
+        if not (isinstance(mvp, list) and len(mvp) == len(f.xy) == frame.N):
+            return None
+        return f
+
+    def _local_loop(self, frame, vpMapPoints, th, viewing_cos_limit):
+        """Tracking.search_local_points' loop with the frame's own is_in_frustum and search_by_projection_f_p: the
+        fallback of search_local_points."""
+        nToMatch = 0
+        for pMP in vpMapPoints:
+            if pMP.mnLastFrameSeen == frame.mnId:
+                continue
+            if pMP.is_bad():
+                continue
+            if frame.is_in_frustum(pMP, viewing_cos_limit):
+                pMP.increase_visible()
+                nToMatch += 1
+        return nToMatch, (self.search_by_projection_f_p(frame, vpMapPoints, th) if nToMatch > 0 else None)
+
+    def _fp_one(self, frame, pMP, th):
+        """The body of search_by_projection_f_p's loop (ORBMatcher.py:226-281) for one point that is tracked in view
+        and not bad, with the reference's expressions on the objects against the current frame.mvpMapPoints, raising
+        what they raise; the few distances are host popcounts.  True when the point was assigned."""
+        b_factor = th != 1.0
+        n_predicted_level = pMP.mnTrackScaleLevel
+        r = self.radius_by_viewing_cos(pMP.mTrackViewCos)
+        if b_factor:
+            r *= th
+        v_indices = frame.get_features_in_area(pMP.mTrackProjX, pMP.mTrackProjY,
+                                               r * frame.mvScaleFactors[n_predicted_level], n_predicted_level - 1,
+                                               n_predicted_level)
+        if not v_indices:
+            return False
+        MPdescriptor = pMP.get_descriptor()
+        best_dist = 256
+        best_level = -1
+        best_dist2 = 256
+        best_level2 = -1
+        best_idx = -1
+        for idx in v_indices:
+            if frame.mvpMapPoints[idx]:
+                if frame.mvpMapPoints[idx].observations() > 0:
+                    continue
+            if frame.mvuRight[idx] > 0:
+                er = abs(pMP.mTrackProjXR - frame.mvuRight[idx])
+                if er > r * frame.mvScaleFactors[n_predicted_level]:
+                    continue
+            dist = descriptor_distance(MPdescriptor, frame.mDescriptors[idx])
+            if dist < best_dist:
+                best_dist2 = best_dist
+                best_dist = dist
+                best_level2 = best_level
+                best_level = frame.mvKeysUn[idx].octave
+                best_idx = idx
+            elif dist < best_dist2:
+                best_level2 = frame.mvKeysUn[idx].octave
+                best_dist2 = dist
+        if best_dist <= TH_HIGH:
+            if best_level == best_level2 and best_dist > self.mfNNratio * best_dist2:
+                return False
+            frame.mvpMapPoints[best_idx] = pMP
+            return True
+        return False
+
+    @classmethod
+    def _local_points(cls, vp, mn_id):
+        """_search_points for search_local_points, whose lists are long and run on every frame: the loop's two skips
+        in list order, then the kept points' positions, normals, distances and descriptors gathered by C-level map()
+        and stacked once where they are uniform (arrays of one shape and dtype each, distances of _DIST_SET); a row
+        that is not finite is a point the arrays cannot express.  Anything else takes _search_points point by point.
+        Returns (slot per list position, (m, 9) rows, (m, 32) descriptors, any float32)."""
+        skip = [p.mnLastFrameSeen == mn_id or p.is_bad() for p in vp]
+        kept = list(compress(vp, map(operator.not_, skip)))
+        m = len(kept)
+        pos, nrm = list(map(_WORLD_POS, kept)), list(map(operator.methodcaller("get_normal"), kept))
+        d3 = (list(map(operator.methodcaller("get_min_distance_invariance"), kept)),
+              list(map(operator.methodcaller("get_max_distance_invariance"), kept)),
+              list(map(operator.attrgetter("mfMaxDistance"), kept)))
+        descs = list(map(_DESCRIPTOR, kept))
+
+        def uniform(arrs, shapes, dts):
+            return (set(map(type, arrs)) == _NDARRAY_SET and len(set(map(_SHAPE, arrs))) == 1
+                    and arrs[0].shape in shapes and len(set(map(_DTYPE, arrs))) == 1 and arrs[0].dtype in dts)
+        if not (m and uniform(pos, ((3, 1),), _POSE_DT) and uniform(nrm, ((3, 1),), _POSE_DT)
+                and uniform(descs, ((32,), (1, 32), (32, 1)), (_U8_DT,))
+                and all(set(map(type, d)) <= _DIST_SET for d in d3)):
+            skipped = iter(skip)
+            slot, rows, descs, f32 = cls._search_points(vp, lambda p: next(skipped), f32_dist=True)
+            return (np.array(slot, np.int64).reshape(-1), np.array(rows, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64),
+                    np.array(descs, np.uint8).reshape(-1, 32), f32)
+        rows = np.empty((m, _lib.ORBFE_FUSE_PT_F64), np.float64)
+        rows[:, 0:3] = np.concatenate(pos).reshape(m, 3)
+        rows[:, 3:6] = np.concatenate(nrm).reshape(m, 3)
+        for c, d in enumerate(d3):
+            rows[:, 6 + c] = d
+        ok = np.isfinite(rows).all(axis=1)
+        slot = np.full(len(vp), -2, np.int64)
+        at = np.flatnonzero(~np.array(skip, bool))
+        slot[at] = np.where(ok, np.cumsum(ok) - 1, -1)
+        return (slot, rows[ok], np.concatenate(descs).reshape(m, 32)[ok],
+                pos[0].dtype == _F32_DT or nrm[0].dtype == _F32_DT)
+
+    def _local_jobs(self, jobs, th, viewing_cos_limit):
+        """search_local_points for every (frame, vpMapPoints, _local_frame(frame)) of jobs, whose frames are distinct
+        objects with distinct mvpMapPoints lists, from one k_local_search launch of one search per job: the
+        (nToMatch, n_matches) pairs.  Per job in the reference's order: the loop's two skips in list order, the
+        blocked bytes (a slot holding a point with observations) taken once, then after the launch the frustum
+        half and the replay, frame by frame (see search_local_points)."""
+        from .frame import is_in_frustum_many
+        frames, rows, descs, f32, preps, n_rows = [], [], [], False, [], 0
+        srch_off, item_pt, blocked = [0], [], []
+        for frame, vp, f in jobs:
+            slot, rows_j, descs_j, p32 = self._local_points(vp, frame.mnId)
+            sent = np.flatnonzero(slot >= 0)
+            item_pt.append(slot[sent] + n_rows)
+            srch_off.append(srch_off[-1] + len(sent))
+            n_rows += len(rows_j)
+            rows.append(rows_j)
+            descs.append(descs_j)
+            f32 = f32 or p32 or f.f32
+            blocked.append(_blocked(frame))
+            frames.append(f)
+            preps.append((slot, sent))
+        if srch_off[-1]:
+            res = self._search_launch(frames, np.concatenate(rows), np.concatenate(descs), th, f32,
+                                      blocked=np.concatenate(blocked), local=(
+                np.full(len(jobs), float(viewing_cos_limit)), np.arange(len(jobs), dtype=np.int32),
+                np.array(srch_off, np.int64), np.concatenate(item_pt).astype(np.int32), th != 1.0))
+        out = []
+        nnratio = self.mfNNratio
+        for q, ((frame, vp, f), (slot, sent)) in enumerate(zip(jobs, preps)):
+            # the frustum half: what an unmarked item decided stands; the attributes, and the decision of a marked
+            # item or of a point the arrays cannot express, come from the reference's expressions on the host
+            dev = {}
+            if len(sent):
+                seg = slice(srch_off[q], srch_off[q + 1])
+                st, view = res["status"][seg], res["in_view"][seg]
+                for i in sent[(st == 0) & (view == 0)].tolist():
+                    vp[i].mbTrackInView = False
+                live = (st != 0) | (view != 0)
+                dev = dict(zip(sent[live].tolist(), zip(
+                    st[live].tolist(), res["level"][seg][live].tolist(), res["best_idx"][seg][live].tolist(),
+                    res["best_dist"][seg][live].tolist(), res["second_idx"][seg][live].tolist(),
+                    res["second_dist"][seg][live].tolist())))
+            host = sorted(list(dev) + np.flatnonzero(slot == -1).tolist())
+            seen = dict(zip(host, is_in_frustum_many(frame, [vp[i] for i in host], viewing_cos_limit)))
+            nToMatch = 0
+            for i in host:
+                if seen[i]:
+                    vp[i].increase_visible()
+                    nToMatch += 1
+            if nToMatch == 0:
+                out.append((0, None))
+                continue
+            # the replay of search_by_projection_f_p, in list order
+            mvp, kps = frame.mvpMapPoints, frame.mvKeysUn
+            n_matches = 0
+            for i in sorted(np.flatnonzero(slot == -2).tolist() + [i for i in host if seen[i]]):
+                pMP = vp[i]
+                d = dev.get(i)
+                if slot[i] == -2:
+                    # skipped by the loop above: searched where it is still tracked in view from an earlier frame
+                    if not pMP.mbTrackInView or pMP.is_bad():
+                        continue
+                    d = None
+                if d is not None and not d[0] and pMP.mnTrackScaleLevel == d[1]:
+                    _, _, bi, bd, si, sd = d
+                    # what is left of a point's candidates is never closer than its best: an unmarked item above
+                    # TH_HIGH, or without a candidate, assigns nothing whatever was taken meanwhile
+                    if bi < 0 or bd > TH_HIGH:
+                        continue
+                    m, m2 = mvp[bi], (mvp[si] if si >= 0 else None)
+                    if not ((m and m.observations() > 0) or (m2 and m2.observations() > 0)):
+                        # a distance of 256 never enters the reference's second place
+                        best_level2, best_dist2 = (kps[si].octave, sd) if si >= 0 and sd < 256 else (-1, 256)
+                        if kps[bi].octave == best_level2 and bd > nnratio * best_dist2:
+                            continue
+                        mvp[bi] = pMP
+                        n_matches += 1
+                        continue
+                if self._fp_one(frame, pMP, th):
+                    n_matches += 1
+            out.append((nToMatch, n_matches))
+        return out
+
+    def search_local_points(self, frame, vpMapPoints, th, viewing_cos_limit=0.5):
+        """Tracking.search_local_points (Tracking.py:439-468) from one k_local_search launch: what this gives, return
+        values and side effects in the same order,
+
+            nToMatch = 0
+            for pMP in vpMapPoints:
+                if pMP.mnLastFrameSeen == frame.mnId: continue
+                if pMP.is_bad(): continue
+                if frame.is_in_frustum(pMP, viewing_cos_limit):
+                    pMP.increase_visible(); nToMatch += 1
+            n = self.search_by_projection_f_p(frame, vpMapPoints, th) if nToMatch > 0 else None
+
+        as (nToMatch, n).  The points the loop does not skip are packed once and launched, with
+        blocked[i] = mvpMapPoints[i] holds a point with observations, taken once.  in_view and level of an item that
+        did not come back ORBFE_FUSE_MARGINAL stand; a marked item, and a point the arrays cannot express, is decided
+        by the reference's expressions.  Every attribute is_in_frustum writes comes from frame.is_in_frustum_many on
+        the host, never from the kernel.  Then the replay in list order: an item's best candidate is assigned when it
+        passes TH_HIGH and the ratio test against the second (on the host, with the Python operands); an item is
+        redone alone against the current mvpMapPoints with the reference's expressions (_fp_one) when it is marked,
+        when its best or second feature has meanwhile been taken by a point with observations, or when the loop
+        skipped its point but the point is still tracked in view (it is searched with its stored projections, at its
+        place in the list).  Taking candidates away never makes a remaining one closer, so an unmarked item above
+        TH_HIGH needs no redo (see search_by_projection_f_kf_f).  The loop itself, with frame.is_in_frustum and
+        search_by_projection_f_p, runs instead when the HIP runtime sees no device, when th or the limit is not a
+        plain finite number, when radius_by_viewing_cos is overridden, when frame.mvpMapPoints is not a list of N
+        entries, or when _local_frame refuses the frame."""
+        if _lib.device_present():
+            f = self._local_job(frame, th, viewing_cos_limit)
+            if f is not None:
+                return self._local_jobs([(frame, list(vpMapPoints), f)], th, viewing_cos_limit)[0]
+        return self._local_loop(frame, vpMapPoints, th, viewing_cos_limit)
+
+    def search_local_points_many(self, frames, lists, th, viewing_cos_limit=0.5):
+        """[self.search_local_points(f, vp, th, viewing_cos_limit) for f, vp in zip(frames, lists)], value for value
+        and side effect for side effect, from one k_local_search launch of one search per frame; the frustum halves
+        and the replays go frame by frame, in order.  A frame that cannot take the device path takes the single call
+        at its place.  The loop itself runs when a frame object, or an mvpMapPoints list, occurs twice (its second
+        search would read what the first assigned) and where the HIP runtime sees no device.  A map point may occur
+        in several lists: the kernel reads only what no search writes, and each frame's frustum half rewrites the
+        point's attributes before that frame's replay, as the loop does."""
+        frames, lists = list(frames), [list(vp) for vp in lists]
+        if len(frames) != len(lists):
+            raise ValueError("one map point list per frame")
+        res = [None] * len(frames)
+        distinct = len({id(f) for f in frames}) == len(frames) == len({id(getattr(f, "mvpMapPoints", f))
+                                                                      for f in frames})
+        if frames and distinct and _lib.device_present():
+            packed = [self._local_job(f, th, viewing_cos_limit) for f in frames]
+            take = [k for k, f in enumerate(packed) if f is not None]
+            if take:
+                for k, r in zip(take, self._local_jobs([(frames[k], lists[k], packed[k]) for k in take], th,
+                                                       viewing_cos_limit)):
+                    res[k] = r
+        return [self.search_local_points(f, vp, th, viewing_cos_limit) if r is None else r
+                for f, vp, r in zip(frames, lists, res)]
 
     def _fkf_host(self, CurrentFrame, pKF, sAlreadyFound, th, ORBdist):
         """search_by_projection_f_kf_f on the host, point by point (only the Hamming distances run on the device):
