@@ -772,11 +772,14 @@ void prof_mark(orbfe_ctx& c, hipStream_t s, int k) {
 // k_resize_cascade strips (see the kernel): S strips of the top level's rows, and below it, level by level,
 // the rows strip s owns (a partition: the first source row of its next-level rows onwards) and the rows it
 // computes (its own plus the source rows of the next level's computed rows).  Null when the LDS the strips
-// need exceeds 150 KiB.
+// need exceeds 150 KiB, or when a derived level has more 4-pixel groups than a strip stages x selectors for
+// (kCasGroups: a level wider than 4 096 px); the per-level launches serve such a geometry.
 std::unique_ptr<orbfe_ctx::Cascade> resize_strips(const orbfe_ctx& c, int S) {
     const Geo& g = c.geo;
     const int L = g.nlevels, top = L - 1;
     if (L < 2 || S < 1 || S > g.lv[top].h) return nullptr;
+    for (int l = 1; l < L; ++l)
+        if ((g.lv[l].w + 3) / 4 > kCasGroups) return nullptr;
     std::vector<std::vector<int>> own(L, std::vector<int>(S + 1)), clo(L, std::vector<int>(S)), chi(L, std::vector<int>(S));
     for (int k = 0; k <= S; ++k) own[top][k] = (int)((int64_t)k * g.lv[top].h / S);
     auto yt = [&](int l, int dy) -> const ResizeY& { return c.yt[g.lv[l].ytab_off + dy]; };

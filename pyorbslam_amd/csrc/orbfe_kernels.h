@@ -100,6 +100,12 @@ size_t octree_bins_lds_bytes(const Geo& g, int maxcell);
 size_t detect_lds_bytes(const Geo& g);
 // k_resize_cascade (all levels in one launch, small batches): strips = n_strips x nlevels x {computed lo, hi,
 // owned lo, hi} int16 (host resize_strips); LDS: buffer A at 0, B at off_b, the x selectors at off_x
+constexpr int kCasNT = 1024;      // threads per strip workgroup
+// 4-pixel groups of a derived level whose x selectors a strip stages (a whole number per thread, held in registers
+// while the previous level computes): levels up to 4 096 px.  resize_strips refuses a cascade for a wider level, the
+// launcher too; such geometries take the per-level k_resize_rows launches.
+constexpr int kCasGroups = 1024;
+static_assert(kCasGroups % kCasNT == 0, "k_resize_cascade stages a whole number of groups per thread");
 hipError_t launch_resize_cascade(const Geo& g, const uint8_t* in, int64_t in_pitch, uint8_t* ws, const ResizeX* xt,
                                  const ResizeY* yt, const int16_t* strips, int n_strips, int off_b, int off_x,
                                  int lds_bytes, int n_images, hipStream_t s, int* zero_word = nullptr,

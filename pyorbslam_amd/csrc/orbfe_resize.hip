@@ -257,8 +257,8 @@ __global__ __launch_bounds__(512) void k_resize_rows(Geo g, int l, const uint8_t
 // rows are staged from the input like k_resize_rows; every later level reads the previous level's strip
 // from LDS, ping-ponging between two buffers (A: level 0 staging and even levels, B: odd levels).
 // tab: per (strip, level) int16 {computed lo, hi, owned lo, hi}; offB / offX: byte offsets of buffer B and
-// of the per-level x selector table in the dynamic LDS.
-constexpr int kCasNT = 1024;  // threads per strip workgroup
+// of the per-level x selector table in the dynamic LDS.  (kCasNT threads; no derived level has more than kCasGroups
+// groups: orbfe_kernels.h)
 __global__ __launch_bounds__(kCasNT) void k_resize_cascade(Geo g, const uint8_t* __restrict__ in, int64_t in_pitch,
                                                         uint8_t* __restrict__ ws, const ResizeX* __restrict__ xt,
                                                         const ResizeY* __restrict__ yt, const int16_t* __restrict__ tab,
@@ -296,7 +296,10 @@ __global__ __launch_bounds__(kCasNT) void k_resize_cascade(Geo g, const uint8_t*
     auto s_sx_of = [&](int par) {
         return (lds_i32*)(uintptr_t)(baseA + (uint32_t)offX + (uint32_t)(64 * g.rs_ngrp + par * 4 * g.rs_ngrp));
     };
-    constexpr int kPre = 1024 / kCasNT;  // groups per thread held in registers (levels up to 4 096 px)
+    // groups per thread held in registers: prefetch / commit stage the selectors of a level's first kCasGroups
+    // groups and no more, the row loop walks every group of the level; the host launches no cascade for a
+    // geometry with a derived level of more groups (resize_strips, launch_resize_cascade)
+    constexpr int kPre = kCasGroups / kCasNT;
     uint4 pq0[kPre], pq1[kPre];
     auto prefetch = [&](int l) {
         if (l >= g.nlevels) return;
@@ -488,6 +491,8 @@ hipError_t launch_resize_cascade(const Geo& g, const uint8_t* in, int64_t in_pit
                                  int lds_bytes, int n_images, hipStream_t s, int* zero_word, long long* prof) {
     if (g.nlevels < 2 || n_images <= 0) return hipSuccess;
     if (lds_bytes > lds_limit((const void*)k_resize_cascade)) return hipErrorInvalidConfiguration;  // prepare_resize_cascade was not run
+    for (int l = 1; l < g.nlevels; ++l)
+        if ((g.lv[l].w + 3) / 4 > kCasGroups) return hipErrorInvalidConfiguration;  // more groups than a strip stages
     hipLaunchKernelGGL(k_resize_cascade, dim3(n_strips, n_images), dim3(kCasNT), (size_t)lds_bytes, s, g, in, in_pitch, ws,
                        xt, yt, strips, off_b, off_x, zero_word, prof);
     return hipGetLastError();

@@ -255,8 +255,12 @@ BIG = [(600, 4500), (2300, 4500), (4500, 2500), (600, 16000), (1300, 12000)]
 
 @pytest.mark.parametrize("hw", BIG)
 def test_level_sides_above_4095_px_bit_exact(hw):
-    """One extraction of a 4 500 px wide (or high) image — the cascade pyramid, FAST cells, the octree over
-    a level of more than 4 096 columns (or rows), k_orb — and its sheared pyramid, against the oracle."""
+    """One extraction of a 4 500 px wide (or high) image — the pyramid, FAST cells, the octree over a level of
+    more than 4 096 columns (or rows), k_orb — and its sheared pyramid, against the oracle.  Only the 2 500 px wide
+    image takes the cascade (420 strips on 256 CUs): at 8 levels no strip count of the wide ones fits the LDS (and
+    level 1 of the 12 000 and 16 000 px ones is wider than a cascade's 4 096 px), so their pyramid comes from the
+    per-level k_resize_rows launches (orbfe_debug_cascade_profile, and the restatement in
+    tests/resize_cascade_cases.py)."""
     h, w = hw
     img = synth.make_pair(410 + w % 7, w, h)[0]
     ex = ORBextractor(**KITTI)
