@@ -77,6 +77,22 @@ def test_oracle_and_replay_reproduce_the_reference(golden):
     assert abs(filled - jobs[0][0].N // 4) <= 1 and golden["kf0_T"].dtype == np.float32
 
 
+@pytest.mark.parametrize("seed", [51, 52, 53])
+def test_unmarked_items_decide_as_the_reference_and_few_are_marked(seed):
+    """The soundness of the bound on random float32 worlds, in the golden's configurations: wherever the oracle leaves
+    the status 0, its winner and distance are those of the reference's loop body on the objects.  At most 2 % of the
+    items that reach a cell window may be marked."""
+    import fuse_cases as FC
+    g = FC.Z(KC.make_extras(FC.clone_world(seed), seed))
+    stats = {}
+    for cfg in range(len(KC.CONFIGS)):
+        KC.drive(g, KC.by_oracle(stats, agree=True), cfg)
+    reached, marked = stats["reached"], stats["marginal"]
+    print(f"items {stats['items']} reached {reached} marked {marked} share {marked / reached:.4f}")
+    assert reached > 1000
+    assert marked <= 0.02 * reached
+
+
 # ---- the product with the oracle in the kernel's place ---------------------------------------------------------------
 
 def fake_device(monkeypatch, matcher, launches):

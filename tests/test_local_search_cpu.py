@@ -90,6 +90,40 @@ def test_the_loop_on_the_stand_ins_reproduces_the_reference(golden):
         assert LC.same(got, LC.golden_results(golden, cfg)), cfg
 
 
+@pytest.mark.parametrize("seed", [61, 62, 63])
+def test_unmarked_items_decide_as_the_reference_and_few_are_marked(seed):
+    """The soundness of the bound on random worlds with float32 and float64 poses, at the golden's two values of th:
+    wherever the oracle leaves the status 0, in_view, the level, the winner, both distances and the second's octave
+    are those of the reference's two bodies on the objects.  At most 2 % of the items that reach a cell window may be
+    marked."""
+    import fuse_cases as FC
+    import margin_cases as M
+    g = FC.Z(LC.make_extras(FC.clone_world(seed), seed))
+    items = reached = marked = found = 0
+    for dtype, th in ((np.float32, 1), (np.float64, 5), (np.float32, 5), (np.float64, 1)):
+        jobs, _ = LC.build(g, dtype)
+        a, where = LO.pack(jobs, th, LC.LIMIT)
+        assert a["eps"] == (LO.EPS_F32 if dtype == np.float32 else LO.EPS_F64)
+        out = LO.search(a)
+        for s, (F, vp) in enumerate(jobs):
+            base = int(a["off"][s])
+            for c, i in enumerate(where[s]):
+                j = int(a["srch_off"][s]) + c
+                got = tuple(int(o[j]) for o in out)
+                items += 1
+                if LO._window(a, s, j)[2][2] is not None:
+                    reached += 1
+                    marked += int(got[-1] != 0)
+                if got[-1]:
+                    continue
+                ref, _ = M.local_reference(F, vp[i], LC.LIMIT, th)
+                assert M.same_as_reference("local", got, ref, lambda f: int(a["octave"][base + f])), (s, i, got, ref)
+                found += ref[2] >= 0
+    print(f"items {items} reached {reached} marked {marked} share {marked / reached:.4f} found {found}")
+    assert reached > 1000 and found > 500
+    assert marked <= 0.02 * reached
+
+
 # ---- the product with the oracle in the kernel's place -----------------------------------------------------------------
 
 def fake_device(monkeypatch, matcher, launches):
