@@ -45,7 +45,8 @@ extern "C" {
                                * orbfe_scw_search_last_ms and orbfe_scw_out, and orbfe_sim3_search,
                                * orbfe_sim3_search_last_ms and orbfe_sim3_out, and orbfe_fkf_search,
                                * orbfe_fkf_search_last_ms and orbfe_fkf_out, and orbfe_debug_detect_lanes, and
-                               * orbfe_local_search, orbfe_local_search_last_ms and orbfe_local_out */
+                               * orbfe_local_search, orbfe_local_search_last_ms and orbfe_local_out, and
+                               * orbfe_ff_search, orbfe_ff_search_last_ms and orbfe_ff_out */
 /* frames whose sheared pyramids the lazy frame path (want_pyramid = 2) keeps on the device */
 #define ORBFE_FRAME_RING 8
 int32_t orbfe_abi_version(void);
@@ -961,6 +962,57 @@ int orbfe_local_search(const double* kf_f64, const int32_t* kf_i32, const int64_
                        double eps, const orbfe_local_out* out);
 /* Kernel time of the last orbfe_local_search (ms, HIP events), for measurement. */
 int orbfe_local_search_last_ms(float* ms);
+
+/* ---- tracking's motion-model search (Tracking.track_with_motion_model: ORBMatcher.search_by_projection_f_f,
+ *      ORBMatcher.py:291-393, with Frame.get_features_in_area, Frame.py:373-416) ----
+ *
+ * k_ff_search, one launch for n_srch searches.  A search is a (current frame, last frame) pair: the target is the
+ * current frame, the items are the last frame's map points, each with the octave of the last frame's keypoint it was
+ * seen at.  For every item it finds the best candidate among the current frame's features; the TH_HIGH test, the
+ * assignment into the current frame's map point slots and the rotation histogram stay with the caller, in the
+ * reference's order, and because an assignment by a point with observations takes a feature away from the items after
+ * it, the caller redoes an item whose best feature was taken meanwhile.
+ * The target arrays are orbfe_local_search's, u_right and `blocked` included, and slot [4] of a block, bf, is read.
+ * The point table is orbfe_fuse_search's, but only the position, slots [0..2], is read: slots [3..8] may hold anything.
+ * What differs from orbfe_local_search: there is no distance gate, no viewing gate and no level prediction; the level
+ * is item_level[i]; th is srch_th[s], one per search (Tracking retries a pair with twice the th); the candidates'
+ * octaves follow srch_mode[s]; only the best candidate comes back.
+ * Per item, in IEEE double in this operation order without contraction (sums of three from the left):
+ *   pc = Rcw p + tcw; pc.z < 0 (the reference's 1 / pc.z < 0): no search.  invz = 1 / pc.z; u = (fx * pc.x) * invz +
+ *   cx, v likewise, ur = u - bf * invz; mnMinX <= u <= mnMaxX and mnMinY <= v <= mnMaxY; level = item_level[i];
+ *   r = srch_th[s] * scale[level]; the cell window is orbfe_fkf_search's, truncated at both ends.
+ *   A candidate is an entry of the window's cells in orbfe_scw_search's visiting order whose blocked byte is 0, with
+ *   |x - u| < r and |y - v| < r, its octave in [level - 1, level + 1] (srch_mode[s] == 0), in [level, inf) (1: the
+ *   camera moved forward) or in [0, level] (2: backward), and, where u_right[f] > 0, |ur - u_right[f]| <= r.
+ *   best is the candidate of the smallest key (Hamming distance, visiting position).
+ * Outputs at [i], i < srch_off[n_srch], flat over the items: best_idx, best_dist (-1 for none), status.  status gets
+ * ORBFE_FUSE_MARGINAL under orbfe_local_search's bounds for what the two share (the sign of pc.z, an image bound, a
+ * window bound near an integer of magnitude >= 1, a visited entry's |dx| or |dy| near r, the stereo gate near r; a
+ * blocked entry marks nothing; the octave tests are integer tests) and for pc.z == 0 of either sign, which gets no
+ * candidate (the reference's 1 / 0 gives inf or NaN, whose comparisons can let the point through to an int(nan) that
+ * raises), and for an intermediate that is not finite.  The outputs of a marked item are this arithmetic's.  The
+ * limits are orbfe_fuse_search's.  A workgroup takes up to ORBFE_FUSE_CHUNK items of one search; an empty search
+ * launches nothing. */
+typedef struct orbfe_ff_out {
+    int32_t* best_idx;  /* one per item */
+    int32_t* best_dist; /* one per item */
+    uint8_t* status;    /* one per item */
+} orbfe_ff_out;
+/* Host buffers, synchronous; the target arrays and their checks are orbfe_local_search's; the searches' checks are
+ * orbfe_fkf_search's, and ORBFE_EINVAL, before any device call, also for a srch_th that is not finite, a srch_mode
+ * outside 0..2, an item_level outside [0, levels) of the item's target, and a point position that is not finite
+ * (slots [3..8] are not looked at).  n_srch == 0 or srch_off[n_srch] == 0 launches nothing and succeeds.  Process-wide
+ * buffers, stream and events of its own: concurrent callers take turns, and none of them waits for a caller of the
+ * other five searches. */
+int orbfe_ff_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                    const int32_t* octave, const double* u_right, const uint8_t* desc32, const uint8_t* blocked,
+                    const int64_t* cell_at, const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx,
+                    const int64_t* lvl_off, const double* scale, int32_t n_kf, const double* pt_f64,
+                    const uint8_t* pt_desc32, int64_t n_pts, const double* srch_th, const int32_t* srch_mode,
+                    const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt,
+                    const int32_t* item_level, double eps, const orbfe_ff_out* out);
+/* Kernel time of the last orbfe_ff_search (ms, HIP events), for measurement. */
+int orbfe_ff_search_last_ms(float* ms);
 
 /* ---- place recognition (KeyFrameDatabase.py, pyDBoW/ScoringObject.py) ------------------
  *

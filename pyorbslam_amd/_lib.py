@@ -118,6 +118,11 @@ class LocalOut(C.Structure):
                                           "status")]
 
 
+class FfOut(C.Structure):
+    """orbfe_ff_out: caller-owned output arrays of orbfe_ff_search, flat over the items."""
+    _fields_ = [(k, C.c_void_p) for k in ("best_idx", "best_dist", "status")]
+
+
 class KfdbManyOut(C.Structure):
     """orbfe_kfdb_many_out: caller-owned host arrays of orbfe_kfdb_query_many / _many_device."""
     _fields_ = [(k, C.c_void_p) for k in ("n_sharing", "max_common", "n_hits", "hit_slot", "hit_common", "hit_first",
@@ -258,6 +263,10 @@ SIGNATURES = {
                                                C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_double,
                                                C.POINTER(LocalOut)],
     "orbfe_local_search_last_ms": [C.POINTER(C.c_float)],
+    "orbfe_ff_search": [C.c_void_p] * 14 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                            C.POINTER(FfOut)],
+    "orbfe_ff_search_last_ms": [C.POINTER(C.c_float)],
 }
 
 _lib: C.CDLL | None = None

@@ -4,8 +4,9 @@
 // k_scw_search; and the two directions of ORBMatcher.search_by_sim3 (:713-848) for many keyframe pairs as
 // k_sim3_search; and relocalisation's ORBMatcher.search_by_projection_f_kf_f (:924-1008) into many frames as
 // k_fkf_search; and tracking's local-map search, Frame.is_in_frustum (Frame.py:328-371) followed by
-// ORBMatcher.search_by_projection_f_p (:215-283), as k_local_search.  All five kernels are instantiations of one body,
-// proj_search<kMode>.
+// ORBMatcher.search_by_projection_f_p (:215-283), as k_local_search; and tracking's motion-model search,
+// ORBMatcher.search_by_projection_f_f (:291-393), for many (current frame, last frame) pairs as k_ff_search.  All six
+// kernels are instantiations of one body, proj_search<kMode>.
 //
 // The reference projects each map point into a keyframe, gates it (depth sign, image bounds, scale-invariance
 // distances, viewing angle), predicts its pyramid level, searches the keyframe's grid in a window of radius
@@ -53,6 +54,14 @@
 //                  per candidate (a feature whose right coordinate is > 0 is left out when |ur - uR| > r); and the
 //                  second smallest key besides the smallest.  It also gives what is_in_frustum decides: in_view and
 //                  the level, which stand whatever becomes of the window.
+//
+//   k_ff_search    is k_local_search's Frame target, ragged launch, blocked byte, depth gate, ur and per-candidate
+//                  stereo gate, without any gate on the point itself: no distance gate, no viewing gate and no level
+//                  prediction (slots 3-8 of a point's scalars are not read).  The level is the item's own (item_level,
+//                  the octave of the last frame's keypoint), th is the search's (one double per search, where
+//                  k_local_search has its cosine limit), and a per-search mode chooses the candidates' octaves:
+//                  [level - 1, level + 1], [level, inf) when the camera moved forward, [0, level] when backward.  Only
+//                  the smallest key comes back.
 //
 // The depth gate: fuse_pkf_mp and fuse_kf_scw_mp skip z < 0, the ckf search z <= 0.  At z == 0 the first two run on to
 // 1 / 0, u and v become inf or NaN and fail the image test, so all three skip the point and one code path serves them.
@@ -132,7 +141,13 @@ struct PsSim3 {
     const int64_t* chunk;    // (search, first item) per workgroup
 };
 
-enum PsMode { kPsFuse, kPsScw, kPsSim3, kPsFkf, kPsLocal };
+// k_ff_search only: what a search and an item have besides PsSim3 (whose f64 holds one double per search, its th)
+struct PsFf {
+    const int32_t* mode;        // per search: 0 [level - 1, level + 1], 1 forward [level, inf), 2 backward [0, level]
+    const int32_t* item_level;  // per item, beside item_pt: the octave of the last frame's keypoint
+};
+
+enum PsMode { kPsFuse, kPsScw, kPsSim3, kPsFkf, kPsLocal, kPsFf };
 
 // every margin test is strict: a bound of zero means every summed term was zero, and then the reference's value
 // is this one exactly
@@ -141,15 +156,17 @@ __device__ __forceinline__ bool near_int(double a, double e) { return fabs(a - r
 template <PsMode kMode>
 __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, double th, double eps,
                                             const PsOut& out, [[maybe_unused]] const PsSim3& sx,
-                                            [[maybe_unused]] int th_on = 0) {
+                                            [[maybe_unused]] int th_on = 0,
+                                            [[maybe_unused]] const PsFf& ff = PsFf{}) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode == kPsScw, kSim3 = kMode == kPsSim3;
-    constexpr bool kLocal = kMode == kPsLocal;
+    constexpr bool kLocal = kMode == kPsLocal, kFf = kMode == kPsFf;
+    constexpr bool kGate = kLocal || kFf;  // the depth gate's mark at zero and the per-candidate stereo gate
     // a Frame target: the reference's (fx * xc) * invz, inclusive bounds, a window truncated at both ends
-    constexpr bool kFkf = kMode == kPsFkf || kLocal;
+    constexpr bool kFkf = kMode == kPsFkf || kGate;
     constexpr bool kDepthFree = kMode == kPsFkf;  // no depth gate
     constexpr bool kRagged = kSim3 || kFkf;  // a 1-D grid over the chunk table, outputs flat over the items
     constexpr bool kBlocked = kScw || kFkf;
-    constexpr bool kRight = kFuse || kLocal;  // projects ur = u - bf / z
+    constexpr bool kRight = kFuse || kGate;  // projects ur = u - bf / z
     __shared__ double s_u[kPsChunk], s_v[kPsChunk], s_eu[kPsChunk], s_ev[kPsChunk], s_r[kPsChunk];
     __shared__ double s_ur[kPsChunk], s_eur[kPsChunk];  // referenced, and so allocated, where kRight only
     __shared__ int16_t s_x0[kPsChunk], s_x1[kPsChunk], s_y0[kPsChunk], s_y1[kPsChunk], s_lvl[kPsChunk];
@@ -262,7 +279,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 if constexpr (!kDepthFree) {
                     if (zc < Ez) st = ORBFE_FUSE_MARGINAL;
                     // k_local_search: the reference's NaN comparisons may let the point through its bounds
-                    if constexpr (kLocal)
+                    if constexpr (kGate)
                         if (zc == 0.0) st = ORBFE_FUSE_MARGINAL;
                     if (zc == 0.0) break;  // not in the image (in is false), whatever xc and yc are
                 }
@@ -297,6 +314,32 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     fabs(v - minY) < Ev + eps * fabs(minY) || fabs(v - maxY) < Ev + eps * fabs(maxY))
                     st = ORBFE_FUSE_MARGINAL;
                 if (!in) break;
+                if constexpr (kFf) {
+                    // no gate on the point and no prediction: the level is the item's own, th the search's.  The
+                    // window below is the Frame window further down, statement for statement: sharing it through a
+                    // nested block or a lambda changes the register allocation of the other five kernels
+                    const int level = ff.item_level[i];
+                    r = sx.f64[srch] * scale[level];
+                    const double ax = ((u - minX) - r) * winv, bx = ((u - minX) + r) * winv;
+                    const double ay = ((v - minY) - r) * hinv, by = ((v - minY) + r) * hinv;
+                    if (!isfinite((ax + bx) + (ay + by))) {
+                        st = ORBFE_FUSE_MARGINAL;
+                        break;
+                    }
+                    const double Ewx = fabs(winv) * (Eu + 4.0 * eps * ((fabs(u) + fabs(minX)) + fabs(r)));
+                    const double Ewy = fabs(hinv) * (Ev + 4.0 * eps * ((fabs(v) + fabs(minY)) + fabs(r)));
+                    if ((fabs(ax) > 0.5 && near_int(ax, Ewx)) || (fabs(bx) > 0.5 && near_int(bx, Ewx)) ||
+                        (fabs(ay) > 0.5 && near_int(ay, Ewy)) || (fabs(by) > 0.5 && near_int(by, Ewy)))
+                        st = ORBFE_FUSE_MARGINAL;
+                    const double tax = trunc(ax), tbx = trunc(bx), tay = trunc(ay), tby = trunc(by);
+                    if (tax >= (double)cols || tbx < 0.0 || tay >= (double)rows || tby < 0.0) break;
+                    x0 = tax < 0.0 ? 0 : (int)tax;
+                    x1 = tbx > (double)(cols - 1) ? cols - 1 : (int)tbx;
+                    y0 = tay < 0.0 ? 0 : (int)tay;
+                    y1 = tby > (double)(rows - 1) ? rows - 1 : (int)tby;
+                    lvl = level;
+                    break;
+                }
                 [[maybe_unused]] double po0 = 0.0, po1 = 0.0, po2 = 0.0;
                 double dist, Ed;
                 if constexpr (kSim3) {
@@ -433,7 +476,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
     [[maybe_unused]] const uint8_t* blk = nullptr;
     if constexpr (kBlocked) {
         blk = kf.blocked ? kf.blocked + base : nullptr;
-        if constexpr (kLocal) uright = kf.u_right + base;
+        if constexpr (kGate) uright = kf.u_right + base;
     } else if constexpr (kFuse) {
         uright = kf.u_right + base;
         is2 = kf.inv_sigma2 + kf.lvl_off[k];
@@ -460,6 +503,12 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                 pd = reinterpret_cast<const uint4*>(pt.desc + i * 32);
             const uint4 qa = pd[0], qb = pd[1];
             const double er_r = eps * fabs(r);
+            [[maybe_unused]] int olo = 0, ohi = 0;  // k_ff_search: the search's octave range around the item's level
+            if constexpr (kFf) {
+                const int md = ff.mode[srch];
+                olo = md == 1 ? level : (md == 2 ? 0 : level - 1);
+                ohi = md == 1 ? 0x7FFFFFFF : (md == 2 ? level : level + 1);
+            }
             for (int ix = x0; ix <= x1; ++ix) {
                 const int a = coff[ix * rows + y0], b = coff[ix * rows + y1 + 1];
                 for (int pos = a + l; pos < b; pos += kPsGroup) {
@@ -472,7 +521,11 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                     if (fabs(fabs(dx) - r) < Edx + er_r || fabs(fabs(dy) - r) < Edy + er_r) st = ORBFE_FUSE_MARGINAL;
                     if (!(fabs(dx) < r && fabs(dy) < r)) continue;
                     const int o = oct[f];
-                    if (o < level - 1 || o > level + (kFkf && !kLocal ? 1 : 0)) continue;
+                    if constexpr (kFf) {
+                        if (o < olo || o > ohi) continue;
+                    } else {
+                        if (o < level - 1 || o > level + (kFkf && !kLocal ? 1 : 0)) continue;
+                    }
                     if constexpr (kFuse) {
                         const double kr = uright[f];
                         const double ex = u - kx, ey = v - ky;
@@ -494,7 +547,7 @@ __device__ __forceinline__ void proj_search(const PsKfs& kf, const PsPts& pt, do
                         if (!(fabs(chi - T) >= Echi + eps * T)) st = ORBFE_FUSE_MARGINAL;  // a NaN marks too
                         if (chi > T) continue;
                     }
-                    if constexpr (kLocal) {
+                    if constexpr (kGate) {
                         // the per-candidate stereo gate: |ur - uR| > r leaves a feature with a right coordinate out
                         const double kr = uright[f];
                         if (kr > 0.0) {
@@ -567,19 +620,26 @@ __global__ __launch_bounds__(kPsChunk) void k_local_search(PsKfs kf, PsPts pt, d
     proj_search<kPsLocal>(kf, pt, th, eps, out, sx, th_on);
 }
 
+// the same grid; sx.f64 holds one double per search, its th; ff the searches' octave modes and the items' levels
+__global__ __launch_bounds__(kPsChunk) void k_ff_search(PsKfs kf, PsPts pt, double eps, PsOut out, PsSim3 sx,
+                                                        PsFf ff) {
+    proj_search<kPsFf>(kf, pt, 0.0, eps, out, sx, 0, ff);
+}
+
 }  // namespace orbfe
 
 namespace {
 
 // scratch of one entry: process-wide, created on first use and never torn down (the HIP runtime may already be gone
 // when static destructors run); callers of that entry on several threads take turns.  Each entry has an instance of
-// its own, so the four do not wait for each other and each last_ms is its own entry's.
+// its own, so they do not wait for each other and each last_ms is its own entry's.
 struct Searcher {
     std::mutex mu;
     DevBuf<uint8_t> d_u8;   // keyframe descriptors, point descriptors, blocked bytes, status
     DevBuf<double> d_f64;   // keyframe scalars, xy, u_right, scale, inv_sigma2, point scalars, search scalars
     DevBuf<int64_t> d_i64;  // off, cell_at, idx_at, lvl_off, srch_off, chunk table
-    DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, srch_kf, item_pt, best_idx, best_dist
+    DevBuf<int32_t> d_i32;  // keyframe ints, octave, cell_off, cell_idx, srch_kf, item_pt, (item_level, srch_mode,)
+                            // best_idx, best_dist
     std::vector<int32_t> h_i32;
     std::vector<uint8_t> h_st;
     std::vector<int64_t> h_chunk;  // k_sim3_search, k_fkf_search: (search, first item) per workgroup
@@ -595,16 +655,22 @@ std::string at_kf(int32_t k, const std::string& what) { return "keyframe " + std
 
 // what orbfe_sim3_search and orbfe_fkf_search have besides the keyframes and the point table
 struct Sim3In {
-    const double* f64;  // orbfe_fkf_search: null; orbfe_local_search: the viewing cosine's limit per search
+    const double* f64;  // orbfe_fkf_search: null; orbfe_local_search: the viewing cosine's limit per search;
+                        // orbfe_ff_search: th per search
     const int32_t* kf;
     const int64_t* off;
     int32_t n;
     const int32_t* item_pt;
     int th_on = 0;  // orbfe_local_search only
+    // orbfe_ff_search only
+    const int32_t* mode = nullptr;
+    const int32_t* item_level = nullptr;
 };
 
-// All five entries: validate, stage, launch, download.  kPsLocal is kPsFkf with u_right, slot 4 and the normal read,
-// one scalar per search and four more outputs.  Otherwise, not kPsFuse: u_right and inv_sigma2 are not looked at and
+// All six entries: validate, stage, launch, download.  kPsLocal is kPsFkf with u_right, slot 4 and the normal read,
+// one scalar per search and four more outputs.  kPsFf is kPsLocal without those outputs, with th as the search's
+// scalar (the argument th is not looked at), a mode per search and a level per item, and slots 3-8 of a point's
+// scalars free to hold anything.  Otherwise, not kPsFuse: u_right and inv_sigma2 are not looked at and
 // slot 4 of a keyframe's scalars may hold anything.  kPsScw, kPsFkf: blocked may be null (nothing is blocked);
 // otherwise blocked is not looked at.  kPsSim3, kPsFkf: sx is the searches, slots 3-5 of a point's scalars may hold
 // anything, out_stride is not looked at and the outputs are flat over the items; kPsSim3 alone has search scalars and
@@ -617,10 +683,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             const uint8_t* pt_desc32, int64_t n_pts, double th, double eps, const Out* out, int64_t out_stride,
             [[maybe_unused]] const Sim3In* sx = nullptr) {
     constexpr bool kFuse = kMode == kPsFuse, kScw = kMode != kPsFuse, kSim3 = kMode == kPsSim3;
-    constexpr bool kLocal = kMode == kPsLocal;
-    constexpr bool kRight = kFuse || kLocal;  // u_right and slot 4 (bf) are read
-    constexpr bool kRagged = kSim3 || kMode == kPsFkf || kLocal;
-    constexpr bool kBlocked = kMode == kPsScw || kMode == kPsFkf || kLocal;
+    constexpr bool kLocal = kMode == kPsLocal, kFf = kMode == kPsFf;
+    constexpr bool kRight = kFuse || kLocal || kFf;  // u_right and slot 4 (bf) are read
+    constexpr bool kRagged = kSim3 || kMode == kPsFkf || kLocal || kFf;
+    constexpr bool kBlocked = kMode == kPsScw || kMode == kPsFkf || kLocal || kFf;
     constexpr size_t kOutI32 = kLocal ? 5 : 2, kOutU8 = kLocal ? 2 : 1;  // output arrays per item
     if (n_kf < 0 || n_pts < 0 || out_stride < 0) throw Error(ORBFE_EINVAL, "bad argument");
     if (n_kf > 65535) throw Error(ORBFE_EINVAL, "more than 65535 keyframes in one call");
@@ -637,7 +703,9 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": srch_off must not decrease");
         n_items = sx->off[sx->n];
         if (n_items == 0) return;
-        if (((kSim3 || kLocal) && !sx->f64) || !sx->kf || !sx->item_pt) throw Error(ORBFE_EINVAL, "null argument");
+        if (((kSim3 || kLocal || kFf) && !sx->f64) || !sx->kf || !sx->item_pt ||
+            (kFf && (!sx->mode || !sx->item_level)))
+            throw Error(ORBFE_EINVAL, "null argument");
         for (int32_t q = 0; q < sx->n; ++q) {
             if (sx->kf[q] < 0 || sx->kf[q] >= n_kf)
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the target is outside the keyframes");
@@ -645,6 +713,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": a scalar is not finite");
             if (kLocal && !std::isfinite(sx->f64[q]))
                 throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the viewing cosine's limit is not finite");
+            if (kFf && !std::isfinite(sx->f64[q]))
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": th is not finite");
+            if (kFf && (sx->mode[q] < 0 || sx->mode[q] > 2))
+                throw Error(ORBFE_EINVAL, "search " + std::to_string(q) + ": the mode is outside 0..2");
         }
         for (int64_t i = 0; i < n_items; ++i)
             if (sx->item_pt[i] < 0 || sx->item_pt[i] >= n_pts)
@@ -702,7 +774,19 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
             if (f < 0 || f >= n) throw Error(ORBFE_EINVAL, at_kf(k, "a grid entry is outside the features"));
         }
     }
-    if constexpr (kRagged && !kLocal) {
+    if constexpr (kFf) {
+        // levels are positive here; an item's level indexes its target's scale table
+        for (int32_t q = 0; q < sx->n; ++q) {
+            const int32_t levels = kf_i32[3 * sx->kf[q] + 2];
+            for (int64_t i = sx->off[q]; i < sx->off[q + 1]; ++i)
+                if (sx->item_level[i] < 0 || sx->item_level[i] >= levels)
+                    throw Error(ORBFE_EINVAL,
+                                "search " + std::to_string(q) + ": an item's level is outside the target's");
+        }
+        for (int64_t i = 0; i < n_pts; ++i)  // only the position is read
+            if (!all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64, 3))
+                throw Error(ORBFE_EINVAL, "a point scalar is not finite");
+    } else if constexpr (kRagged && !kLocal) {
         for (int64_t i = 0; i < n_pts; ++i)  // slots 3-5, the normal, are not read
             if (!(all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64, 3) && all_finite(pt_f64 + i * ORBFE_FUSE_PT_F64 + 6, 3)))
                 throw Error(ORBFE_EINVAL, "a point scalar is not finite");
@@ -736,9 +820,9 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     // descriptors are read as uint4: both blocks start on 16 bytes
     m.d_u8.ensure(pad_to(n * 32, 16) + pad_to(np * 32, 16) + n_blk + kOutU8 * n_out);
     m.d_f64.ensure(nk * ORBFE_FUSE_KF_F64 + 2 * n + n_ur + nl + n_is2 + np * ORBFE_FUSE_PT_F64 +
-                   (kSim3 ? ns * ORBFE_SIM3_F64 : kLocal ? ns : 0));
+                   (kSim3 ? ns * ORBFE_SIM3_F64 : (kLocal || kFf) ? ns : 0));
     m.d_i64.ensure(4 * (nk + 1) + (kRagged ? ns + 1 + 2 * n_chunk : 0));
-    m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + kOutI32 * n_out);
+    m.d_i32.ensure(3 * nk + n + nc + ni + (kRagged ? ns + n_out : 0) + (kFf ? n_out + ns : 0) + kOutI32 * n_out);
     uint8_t* d_desc = m.d_u8.p;
     uint8_t* d_pdesc = d_desc + pad_to(n * 32, 16);
     uint8_t* d_blk = d_pdesc + pad_to(np * 32, 16);
@@ -762,7 +846,9 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     int32_t* d_cidx = d_coff + nc;
     [[maybe_unused]] int32_t* d_skf = d_cidx + ni;
     [[maybe_unused]] int32_t* d_item = d_skf + ns;
-    int32_t* d_bi = kRagged ? d_item + n_out : d_cidx + ni;
+    [[maybe_unused]] int32_t* d_ilvl = d_item + n_out;  // k_ff_search only, as d_mode
+    [[maybe_unused]] int32_t* d_mode = d_ilvl + n_out;
+    int32_t* d_bi = kFf ? d_mode + ns : (kRagged ? d_item + n_out : d_cidx + ni);
     int32_t* d_bd = d_bi + n_out;
     auto up = [&](void* dst, const void* src, size_t bytes) {
         if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
@@ -787,12 +873,16 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     [[maybe_unused]] PsSim3 dsx{};
     if constexpr (kRagged) {
         if constexpr (kSim3) up(d_sx, sx->f64, ns * ORBFE_SIM3_F64 * sizeof(double));
-        if constexpr (kLocal) up(d_sx, sx->f64, ns * sizeof(double));
+        if constexpr (kLocal || kFf) up(d_sx, sx->f64, ns * sizeof(double));
+        if constexpr (kFf) {
+            up(d_ilvl, sx->item_level, n_out * sizeof(int32_t));
+            up(d_mode, sx->mode, ns * sizeof(int32_t));
+        }
         up(d_soff, sx->off, (ns + 1) * sizeof(int64_t));
         up(d_chunk, m.h_chunk.data(), 2 * n_chunk * sizeof(int64_t));
         up(d_skf, sx->kf, ns * sizeof(int32_t));
         up(d_item, sx->item_pt, n_out * sizeof(int32_t));
-        dsx = PsSim3{kSim3 || kLocal ? d_sx : nullptr, d_skf, d_soff, d_item, d_chunk};
+        dsx = PsSim3{kSim3 || kLocal || kFf ? d_sx : nullptr, d_skf, d_soff, d_item, d_chunk};
     }
     PsKfs kf{};
     kf.f64 = d_kf;
@@ -815,7 +905,10 @@ void search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, con
     const PsOut d{d_bi, d_bd, d_st, out_stride, kLocal ? d_bd + n_out : nullptr, kLocal ? d_bd + 2 * n_out : nullptr,
                   kLocal ? d_bd + 3 * n_out : nullptr, kLocal ? d_st + n_out : nullptr};
     m.t.begin(s);
-    if constexpr (kLocal) {
+    if constexpr (kFf) {
+        hipLaunchKernelGGL(k_ff_search, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, eps, d, dsx,
+                           PsFf{d_mode, d_ilvl});
+    } else if constexpr (kLocal) {
         hipLaunchKernelGGL(k_local_search, dim3((unsigned)n_chunk), dim3(kPsChunk), 0, s, kf, pt, th, eps, d, dsx,
                            sx->th_on);
     } else if constexpr (kRagged) {
@@ -948,6 +1041,24 @@ int orbfe_local_search(const double* kf_f64, const int32_t* kf_i32, const int64_
 
 int orbfe_local_search_last_ms(float* ms) {
     return guarded([&] { last_ms<kPsLocal>(ms); });
+}
+
+int orbfe_ff_search(const double* kf_f64, const int32_t* kf_i32, const int64_t* off, const double* xy,
+                    const int32_t* octave, const double* u_right, const uint8_t* desc32, const uint8_t* blocked,
+                    const int64_t* cell_at, const int32_t* cell_off, const int64_t* idx_at, const int32_t* cell_idx,
+                    const int64_t* lvl_off, const double* scale, int32_t n_kf, const double* pt_f64,
+                    const uint8_t* pt_desc32, int64_t n_pts, const double* srch_th, const int32_t* srch_mode,
+                    const int32_t* srch_kf, const int64_t* srch_off, int32_t n_srch, const int32_t* item_pt,
+                    const int32_t* item_level, double eps, const orbfe_ff_out* out) {
+    return guarded([&] {
+        const Sim3In sx{srch_th, srch_kf, srch_off, n_srch, item_pt, 0, srch_mode, item_level};
+        search<kPsFf>(kf_f64, kf_i32, off, xy, octave, u_right, desc32, blocked, cell_at, cell_off, idx_at, cell_idx,
+                      lvl_off, scale, nullptr, n_kf, pt_f64, pt_desc32, n_pts, 0.0, eps, out, 0, &sx);
+    });
+}
+
+int orbfe_ff_search_last_ms(float* ms) {
+    return guarded([&] { last_ms<kPsFf>(ms); });
 }
 
 }  // extern "C"

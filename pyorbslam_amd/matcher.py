@@ -164,6 +164,7 @@ _UR_SET = frozenset((int, float, np.float32, np.float64))
 _DOUBLE_OR_INT_SET = frozenset((float, int, np.float64))
 _ANGLE = operator.attrgetter("angle")
 _OBSERVATIONS = operator.methodcaller("observations")
+_OCTAVE = operator.attrgetter("octave")
 _IN_VIEW = operator.attrgetter("mbTrackInView")
 _IS_BAD = operator.methodcaller("is_bad")
 _VIEW_COS = operator.attrgetter("mTrackViewCos")
@@ -802,6 +803,71 @@ def local_search_last_ms() -> float:
     return float(ms.value)
 
 
+FF_OUTPUTS = ("best_idx", "best_dist", "status")
+
+
+def ff_search_arrays(kf_f64, kf_i32, off, xy, octave, u_right, desc, blocked, cell_at, cell_off, idx_at, cell_idx,
+                     lvl_off, scale, pt_f64, pt_desc, srch_th, srch_mode, srch_kf, srch_off, item_pt, item_level,
+                     eps) -> dict:
+    """orbfe_ff_search (k_ff_search, include/orbfe.h): the search half of ORBMatcher.search_by_projection_f_f
+    (ORBMatcher.py:291-393, with Frame.get_features_in_area, Frame.py:373-416) for many (current frame, last frame)
+    pairs in one launch.  The target arrays are local_search_arrays' (the current frames), u_right and blocked
+    included; pt_f64 (P, 9) / pt_desc (P, 32) are one shared point table of which only the position is read.  Search
+    s has its th srch_th[s], its octave mode srch_mode[s] (0: [level - 1, level + 1], 1 forward: [level, inf), 2
+    backward: [0, level]), the target srch_kf[s] and the items [srch_off[s], srch_off[s + 1]) of item_pt / item_level
+    (the point's row and the octave of the last frame's keypoint).  Returns best_idx, best_dist int32 (-1: no
+    candidate) and status uint8 (ORBFE_FUSE_MARGINAL), flat over the items."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+    kf_f64 = np.ascontiguousarray(kf_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_KF_F64)
+    kf_i32 = np.ascontiguousarray(kf_i32, np.int32).reshape(-1, 3)
+    pt_f64 = np.ascontiguousarray(pt_f64, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
+    pt_desc = np.ascontiguousarray(pt_desc, np.uint8).reshape(-1, 32)
+    off, cell_at, idx_at, lvl_off = (arr(a, np.int64) for a in (off, cell_at, idx_at, lvl_off))
+    xy, u_right, scale, srch_th = (arr(a, np.float64) for a in (xy, u_right, scale, srch_th))
+    octave, cell_off, cell_idx = arr(octave, np.int32), arr(cell_off, np.int32), arr(cell_idx, np.int32)
+    desc, blocked = arr(desc, np.uint8), arr(blocked, np.uint8)
+    n_kf, n_pts = len(kf_f64), len(pt_f64)
+    if len(kf_i32) != n_kf or len(pt_desc) != n_pts:
+        raise ValueError("kf_i32 / pt_desc do not cover the keyframes / points")
+    for a in (off, cell_at, idx_at, lvl_off):
+        if a is None or len(a) != n_kf + 1:
+            raise ValueError("an offset array does not have one entry per keyframe and one more")
+    if n_kf:
+        n, nc, ni, nl = int(off[-1]), int(cell_at[-1]), int(idx_at[-1]), int(lvl_off[-1])
+        for a, size in ((xy, 2 * n), (octave, n), (u_right, n), (desc, 32 * n), (cell_off, nc), (cell_idx, ni),
+                        (scale, nl)):
+            if size > 0 and (a is None or a.size < size):
+                raise ValueError("a per-keyframe array is shorter than its offsets say")
+        if blocked is not None and blocked.size < n:
+            raise ValueError("blocked does not have one byte per feature")
+    n_srch = 0 if srch_kf is None else int(np.size(srch_kf))
+    srch_kf, srch_off, srch_mode = arr(srch_kf, np.int32), arr(srch_off, np.int64), arr(srch_mode, np.int32)
+    item_pt, item_level = arr(item_pt, np.int32), arr(item_level, np.int32)
+    if srch_kf is None or srch_off is None or srch_off.size != n_srch + 1 or (
+            n_srch and (srch_th is None or srch_th.size != n_srch or srch_mode is None or srch_mode.size != n_srch)):
+        raise ValueError("srch_th / srch_mode / srch_kf / srch_off do not cover the searches")
+    n_items = int(srch_off[-1])
+    if n_items > 0 and (item_pt is None or item_pt.size < n_items or item_level is None or item_level.size < n_items):
+        raise ValueError("item_pt / item_level are shorter than srch_off says")
+    n_items = max(n_items, 0)
+    res = dict(best_idx=np.full(n_items, -1, np.int32), best_dist=np.full(n_items, -1, np.int32),
+               status=np.zeros(n_items, np.uint8))
+    out = _lib.FfOut(**{k: v.ctypes.data for k, v in res.items()})
+    call("orbfe_ff_search", ptr(kf_f64), ptr(kf_i32), ptr(off), ptr(xy), ptr(octave), ptr(u_right), ptr(desc),
+         ptr(blocked), ptr(cell_at), ptr(cell_off), ptr(idx_at), ptr(cell_idx), ptr(lvl_off), ptr(scale), n_kf,
+         ptr(pt_f64), ptr(pt_desc), n_pts, ptr(srch_th), ptr(srch_mode), ptr(srch_kf), ptr(srch_off), n_srch,
+         ptr(item_pt), ptr(item_level), float(eps), C.byref(out))
+    return res
+
+
+def ff_search_last_ms() -> float:
+    """Kernel time of the last ff_search_arrays call (ms, HIP events)."""
+    ms = C.c_float(0.0)
+    call("orbfe_ff_search_last_ms", C.byref(ms))
+    return float(ms.value)
+
+
 # eps of orbfe_fuse_search: the unit of rounding of the reference's arithmetic, with a factor 2 in hand for
 # float32 (2^-24 is its unit roundoff) and the 2^-48 class of k_tri_match for float64
 FUSE_EPS_F32 = 2.0 ** -23
@@ -1011,6 +1077,33 @@ def _local_frame(F):
     f.f64[5:20] = R[0] + t[0] + O[0]
     f.u_right = u_right
     f.f32 = R[1] or t[1] or O[1]
+    return f
+
+
+def _ff_frame(F):
+    """Array form of a current Frame for k_ff_search, with the surface search_by_projection_f_f and
+    Frame.get_features_in_area read: _fkf_frame's (the pose slots from mTcw, which the search projects with), with the
+    bf slot from mbf and the right coordinates of mvuRight as _local_frame takes them.  None when _fkf_frame refuses
+    the frame, when mbf or mvuRight is missing, when mbf is not a plain finite double, or when mvuRight does not hold
+    one finite int / float / np.float32 / np.float64 per feature.  An image bound may be a plain int, as in
+    _local_frame."""
+    f = _fkf_frame(F, int_bounds=True)
+    if f is None:
+        return None
+    try:
+        bf, ur = F.mbf, F.mvuRight
+    except AttributeError:
+        return None
+    if type(bf) not in _F64_SET or not np.isfinite(bf):
+        return None
+    if len(ur) != len(f.xy) or not set(map(type, ur)) <= _UR_SET:
+        return None
+    u_right = _u_right(F)
+    if not np.isfinite(u_right).all():
+        return None
+    f.f64 = f.f64.copy()
+    f.f64[4] = bf
+    f.u_right = u_right
     return f
 
 
@@ -1796,11 +1889,12 @@ class ORBMatcher:
         return slot, rows, descs, f32
 
     @staticmethod
-    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None, fkf=None, local=None):
+    def _search_launch(fr, rows, descs, th, f32, fuse=False, blocked=None, sim3=None, fkf=None, local=None, ff=None):
         """The frames fr and the points (rows, descs) packed into one call of fuse_search_arrays (fuse), of
         scw_search_arrays (with blocked), of sim3_search_arrays (with sim3 = (srch_f64, srch_kf, srch_off,
         item_pt)), of fkf_search_arrays (with blocked and fkf = (srch_kf, srch_off, item_pt)) or of
-        local_search_arrays (with blocked and local = (srch_limit, srch_kf, srch_off, item_pt, th_on))."""
+        local_search_arrays (with blocked and local = (srch_limit, srch_kf, srch_off, item_pt, th_on)) or of
+        ff_search_arrays (with blocked and ff = (srch_th, srch_mode, srch_kf, srch_off, item_pt, item_level))."""
         def offs(lens):
             o = np.zeros(len(fr) + 1, np.int64)
             np.cumsum(lens, out=o[1:])
@@ -1810,7 +1904,9 @@ class ORBMatcher:
                 cat("octave"))
         grid = (offs([len(f.cell_off) for f in fr]), cat("cell_off"), offs([len(f.cell_idx) for f in fr]),
                 cat("cell_idx"), offs([len(f.scale) for f in fr]), cat("scale"))
-        pts = (np.array(rows, np.float64), np.stack(descs), th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
+        # descriptor rows already stacked (an (n, 32) array) stand as they are
+        pts = (np.array(rows, np.float64), descs if type(descs) is np.ndarray and descs.ndim == 2 else np.stack(descs),
+               th, FUSE_EPS_F32 if f32 else FUSE_EPS_F64)
         if fuse:
             return fuse_search_arrays(*head, cat("u_right"), cat("desc"), *grid, cat("inv_sigma2"), *pts)
         if sim3 is not None:
@@ -1820,6 +1916,8 @@ class ORBMatcher:
         if local is not None:
             return local_search_arrays(*head, cat("u_right"), cat("desc"), blocked, *grid, *pts[:2], *local[:4], th,
                                        local[4], pts[3])
+        if ff is not None:
+            return ff_search_arrays(*head, cat("u_right"), cat("desc"), blocked, *grid, *pts[:2], *ff, pts[3])
         return scw_search_arrays(*head, cat("desc"), blocked, *grid, *pts)
 
     def fuse_kf_scw_mp_many(self, kfs, Scws, vpPoints, th, after=None):
@@ -3035,6 +3133,235 @@ class ORBMatcher:
                     res[k] = r
         return [self.search_local_points(f, vp, th, viewing_cos_limit) if r is None else r
                 for f, vp, r in zip(frames, lists, res)]
+
+    # ORBMatcher.py:291-393
+    @staticmethod
+    def _ff_job(cur, last, th):
+        """What one pair of search_by_projection_f_f_many needs before the launch, or None when the pair takes the
+        single call: (_ff_frame(cur), mode, candidates, their octaves).  mode is 1 where the reference's b_forward
+        holds, else 2 where its b_backward holds, else 0, from the reference's own expressions."""
+        if not (type(th) in _TH_SET and np.isfinite(th)):
+            return None
+        try:
+            Tl, lmps, lout, n_last, keys = last.mTcw, last.mvpMapPoints, last.mvbOutlier, last.N, last.mvKeys
+            if not (type(Tl) is np.ndarray and Tl.shape == (4, 4) and Tl.dtype in _POSE_DT
+                    and bool(np.isfinite(Tl).all())):
+                return None
+            f = _ff_frame(cur)
+            if f is None:
+                return None
+            mvp = cur.mvpMapPoints
+            if not (isinstance(mvp, list) and len(mvp) == len(f.xy) == cur.N):
+                return None
+            Rcw, tcw = f.pose[0], f.pose[1]
+            with np.errstate(all="ignore"):
+                twc = -Rcw.T @ tcw
+                Rlw = Tl[:3, :3]
+                tlw = Tl[:3, 3:4]
+                tlc = Rlw @ twc + tlw
+                b_forward = tlc[2] > cur.mb
+                b_backward = -tlc[2] > cur.mb
+            mode = 1 if b_forward else (2 if b_backward else 0)
+            if len(lmps) >= n_last and len(lout) >= n_last:  # the same selection with C-level iteration
+                live = list(compress(range(n_last), map(bool, lmps)))
+                cand = list(compress(live, map(operator.not_, map(lout.__getitem__, live))))
+            else:  # the reference's indexing (and its IndexError)
+                cand = [i for i in range(n_last) if lmps[i] and not lout[i]]
+            octs = list(map(_OCTAVE, map(keys.__getitem__, cand)))
+        except (AttributeError, IndexError, TypeError, ValueError):
+            return None
+        if not set(map(type, octs)) <= _INT_SET or (octs and not 0 <= min(octs) <= max(octs) < int(f.i32[2])):
+            return None
+        return f, mode, cand, octs
+
+    def _ff_one(self, cur, last, i, pMP, th, mode, Rcw, tcw):
+        """(best_dist, best_idx2) of one point of the last frame against the current cur.mvpMapPoints with the
+        reference's own expressions on the objects (ORBMatcher.py:314-367), raising what they raise; the few
+        distances are host popcounts."""
+        with np.errstate(all="ignore"):
+            x3Dw = pMP.get_world_pos()
+            x3Dc = Rcw @ x3Dw + tcw
+            xc, yc, zc = x3Dc[0][0], x3Dc[1][0], x3Dc[2][0]
+            invzc = 1.0 / zc
+            if invzc < 0:
+                return 256, -1
+            u = cur.fx * xc * invzc + cur.cx
+            v = cur.fy * yc * invzc + cur.cy
+            if u < cur.mnMinX or u > cur.mnMaxX:
+                return 256, -1
+            if v < cur.mnMinY or v > cur.mnMaxY:
+                return 256, -1
+            n_last_octave = last.mvKeys[i].octave
+            radius = th * cur.mvScaleFactors[n_last_octave]
+            if mode == 1:
+                v_indices2 = cur.get_features_in_area(u, v, radius, n_last_octave, -1)
+            elif mode == 2:
+                v_indices2 = cur.get_features_in_area(u, v, radius, 0, n_last_octave)
+            else:
+                v_indices2 = cur.get_features_in_area(u, v, radius, n_last_octave - 1, n_last_octave + 1)
+            best_dist, best_idx2 = 256, -1
+            if not v_indices2:
+                return best_dist, best_idx2
+            dMP = pMP.get_descriptor()
+            for i2 in v_indices2:
+                if cur.mvpMapPoints[i2]:
+                    if cur.mvpMapPoints[i2].observations() > 0:
+                        continue
+                if cur.mvuRight[i2] > 0:
+                    ur = u - cur.mbf * invzc
+                    er = abs(ur - cur.mvuRight[i2])
+                    if er > radius:
+                        continue
+                dist = descriptor_distance(dMP, cur.mDescriptors[i2])
+                if dist < best_dist:
+                    best_dist = dist
+                    best_idx2 = i2
+        return best_dist, best_idx2
+
+    def _ff_jobs(self, jobs):
+        """search_by_projection_f_f for every (cur, last, th, _ff_job(cur, last, th)) of jobs, whose current frames
+        are distinct objects with distinct mvpMapPoints lists that no pair reads as its last frame, from one
+        k_ff_search launch of one search per job: the match counts.  Per job in the reference's order: the
+        candidates in list order, the blocked bytes (a slot holding a point with observations) taken once, then
+        after the launch the replay in list order (see search_by_projection_f_f_many)."""
+        frames, rows, descs, f32, preps, n_rows = [], [], [], False, [], 0
+        srch_off, item_pt, item_level, blocked = [0], [], [], []
+        for cur, last, th, (f, mode, cand, octs) in jobs:
+            pts = list(map(last.mvpMapPoints.__getitem__, cand))
+            pos, dsc = list(map(_WORLD_POS, pts)), list(map(_DESCRIPTOR, pts))
+            m = len(pts)
+            if (m and set(map(type, pos)) == _NDARRAY_SET and set(map(_SHAPE, pos)) == {(3, 1)}
+                    and len(set(map(_DTYPE, pos))) == 1 and pos[0].dtype in _POSE_DT
+                    and set(map(type, dsc)) == _NDARRAY_SET and set(map(_DTYPE, dsc)) == {_U8_DT}
+                    and set(map(_SIZE, dsc)) == {32} and len(set(map(_SHAPE, dsc))) == 1):
+                # uniform points, gathered above by C-level map() and stacked once; a row that is not finite is a
+                # point the arrays cannot express
+                P = np.concatenate(pos).reshape(m, 3).astype(np.float64)
+                sent = np.flatnonzero(np.isfinite(P).all(axis=1))
+                rows_j = np.zeros((len(sent), _lib.ORBFE_FUSE_PT_F64), np.float64)
+                rows_j[:, 0:3] = P[sent]
+                descs_j = np.concatenate(dsc).reshape(m, 32)[sent]
+                f32 = f32 or (len(sent) > 0 and pos[0].dtype == _F32_DT)
+                sent = sent.tolist()
+            else:
+                sent, rows_j, descs_j = [], [], []
+                for c, (x, d) in enumerate(zip(pos, dsc)):
+                    pp = _pose_part(x, (3, 1))
+                    if pp is None or not (type(d) is np.ndarray and d.dtype == _U8_DT and d.size == 32):
+                        continue  # redone alone
+                    sent.append(c)
+                    rows_j.append(pp[0] + [0.0] * 6)
+                    descs_j.append(d.reshape(32))
+                    f32 = f32 or pp[1]
+                rows_j = np.array(rows_j, np.float64).reshape(-1, _lib.ORBFE_FUSE_PT_F64)
+                descs_j = np.array(descs_j, np.uint8).reshape(-1, 32)
+            item_pt.append(np.arange(n_rows, n_rows + len(sent), dtype=np.int32))
+            item_level.append(np.array(octs, np.int64)[sent].astype(np.int32))
+            n_rows += len(sent)
+            rows.append(rows_j)
+            descs.append(descs_j)
+            srch_off.append(srch_off[-1] + len(sent))
+            f32 = f32 or f.f32
+            blocked.append(_blocked(cur))
+            frames.append(f)
+            preps.append(sent)
+        if srch_off[-1]:
+            res = self._search_launch(frames, np.concatenate(rows), np.concatenate(descs), 0.0, f32,
+                                      blocked=np.concatenate(blocked), ff=(
+                np.array([float(j[2]) for j in jobs], np.float64), np.array([j[3][1] for j in jobs], np.int32),
+                np.arange(len(jobs), dtype=np.int32), np.array(srch_off, np.int64), np.concatenate(item_pt),
+                np.concatenate(item_level)))
+            bi_all, bd_all, st_all = (res[k].tolist() for k in FF_OUTPUTS)
+        out = []
+        factor = 1.0 / HISTO_LENGTH
+        for q, ((cur, last, th, (f, mode, cand, octs)), sent) in enumerate(zip(jobs, preps)):
+            Rcw, tcw = f.pose[0], f.pose[1]
+            lmps, mvp = last.mvpMapPoints, cur.mvpMapPoints
+            at = dict(zip(sent, range(srch_off[q], srch_off[q + 1])))
+            rot_hist = [[] for _ in range(HISTO_LENGTH)]
+            n_matches = 0
+            for c, i in enumerate(cand):
+                pMP = lmps[i]
+                j = at.get(c)
+                if j is not None and not st_all[j]:
+                    # what is left of a point's candidates is never closer than its best: an unmarked item above
+                    # TH_HIGH, or without a candidate, assigns nothing whatever was taken meanwhile
+                    best_idx2, best_dist = bi_all[j], bd_all[j]
+                    if best_idx2 < 0 or best_dist > TH_HIGH:
+                        continue
+                    m = mvp[best_idx2]
+                    if m and m.observations() > 0:
+                        best_dist, best_idx2 = self._ff_one(cur, last, i, pMP, th, mode, Rcw, tcw)
+                else:
+                    best_dist, best_idx2 = self._ff_one(cur, last, i, pMP, th, mode, Rcw, tcw)
+                if best_dist <= TH_HIGH:
+                    mvp[best_idx2] = pMP
+                    n_matches += 1
+                    if self.mbCheckOrientation:
+                        rot = last.mvKeysUn[i].angle - cur.mvKeysUn[best_idx2].angle
+                        if rot < 0.0:
+                            rot += 360.0
+                        b = round(rot * factor)
+                        if b == HISTO_LENGTH:
+                            b = 0
+                        assert 0 <= b < HISTO_LENGTH
+                        rot_hist[b].append(best_idx2)
+            if self.mbCheckOrientation:
+                # a feature assigned twice stands twice in the histogram and is counted, and rejected, twice
+                ind1, ind2, ind3 = self.compute_three_maxima(rot_hist, HISTO_LENGTH)
+                for b in range(HISTO_LENGTH):
+                    if b not in (ind1, ind2, ind3):
+                        for idx in rot_hist[b]:
+                            mvp[idx] = None
+                            n_matches -= 1
+            out.append(n_matches)
+        return out
+
+    def search_by_projection_f_f_many(self, current_frames, last_frames, th):
+        """What this list holds, value for value and leaving every current frame's mvpMapPoints as the loop leaves it,
+        from one k_ff_search launch of one search per pair:
+
+            [self.search_by_projection_f_f(c, l, th_k) for c, l, th_k in zip(current_frames, last_frames, ths)]
+
+        (several trackers stepped in lockstep running Tracking.track_with_motion_model's search).  th is a plain
+        number for all pairs, or a sequence of one per pair (a tracker retries its pair with twice the th).  Per
+        pair, before the launch: b_forward / b_backward by the reference's expressions, the candidates i with
+        mvpMapPoints[i] and not mvbOutlier[i] in list order, blocked[i2] = the slot holds a point with observations,
+        taken once; eps is float32's where the current pose or a sent position is float32.  After the launch the
+        replay in list order: the device's answer stands unless the item came back ORBFE_FUSE_MARGINAL, its point
+        cannot be expressed as arrays (a position that is not a finite (3, 1) float32 / float64 array, a descriptor
+        that is not 32 bytes of uint8), or its best feature has meanwhile been taken by a point with observations;
+        such an item is redone alone against the current slots with the reference's expressions (_ff_one, raising
+        what they raise).  An unmarked item without a candidate or above TH_HIGH is never redone.  Assignment, the
+        count and the rotation histogram with its rejection follow the reference, including a feature that is
+        assigned twice (a point without observations overwritten) being counted and rejected twice.  A pair takes
+        the single call at its place when its th is not a plain finite number, when either mTcw is not a finite 4 x 4
+        float32 / float64 array, when _ff_frame refuses the current frame, when a candidate's octave is not an int
+        inside the current frame's scale table, or when mvpMapPoints is not a list of N entries.  The loop itself
+        runs when a current frame, or its mvpMapPoints list, occurs twice or also serves as a last frame of the
+        call, and where the HIP runtime sees no device.  A last frame may serve several pairs."""
+        curs, lasts = list(current_frames), list(last_frames)
+        if len(curs) != len(lasts):
+            raise ValueError("one last frame per current frame")
+        if isinstance(th, (list, tuple, np.ndarray)) and np.ndim(th) == 1:
+            ths = list(th)
+            if len(ths) != len(curs):
+                raise ValueError("one th per pair, or one for all")
+        else:
+            ths = [th] * len(curs)
+        res = [None] * len(curs)
+        slots = lambda f: id(getattr(f, "mvpMapPoints", f))  # noqa: E731
+        distinct = (len({id(c) for c in curs}) == len(curs) == len({slots(c) for c in curs})
+                    and not {id(c) for c in curs} & {id(x) for x in lasts}
+                    and not {slots(c) for c in curs} & {slots(x) for x in lasts})
+        if curs and distinct and _lib.device_present():
+            packed = [self._ff_job(c, x, t) for c, x, t in zip(curs, lasts, ths)]
+            take = [k for k, j in enumerate(packed) if j is not None]
+            if take:
+                for k, n in zip(take, self._ff_jobs([(curs[k], lasts[k], ths[k], packed[k]) for k in take])):
+                    res[k] = n
+        return [self.search_by_projection_f_f(c, x, t) if r is None else r
+                for c, x, t, r in zip(curs, lasts, ths, res)]
 
     def _fkf_host(self, CurrentFrame, pKF, sAlreadyFound, th, ORBdist):
         """search_by_projection_f_kf_f on the host, point by point (only the Hamming distances run on the device):
